@@ -6,13 +6,21 @@ lpc_from_cepstrum + frame network + 160 recurrent samples, device-resident
 features and PCM (lpcnet_batch_synthesize_frames; everything inside the timed
 region runs on the GPU).  Workload: BASELINE.json configs[3] -- int8 path,
 1024 streams per GPU (configs[4] shards 1024 streams per GPU, weak scaling).
-configs[1] (batch=1, fp32 and int8) and configs[2] (batch=256) are reported
-alongside in `batch1`, `batch1_fp32`, `batch256`.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints one JSON line.
+Rank 0 prints one JSON line.  A plain run does what the headline needs and no
+more: set-up, preheat and warmup, the K timed frames, the line.  --full adds
+every side measurement (each a run of its own): the frame kernel's timed
+pass, configs[1] (batch=1, fp32 and int8) and configs[2] (batch=256) in
+`batch1`, `batch1_fp32`, `batch256`, the wide-batch, skewed-mask, lockstep
+and host-rcpps lines, the stamped latency run, the live line, the capacity
+ladders, the paced drop-in check, the CPU baselines, and the detail side file.
+--dump-outputs DIR writes the PCM of the last timed frame ([streams][160],
+what a caller of the timed path receives for that frame) to DIR/pcm.npy as
+float32; the model and the features are deterministic, so two builds run
+with the same arguments can be compared sample for sample.
 
 Roofline: algorithmic bytes per stream-sample = the shared
 weight bytes of one sample step (GRU_A/GRU_B weights + idx + biases, plus the
@@ -57,12 +65,12 @@ GATHER_BYTES_PER_STREAM_SAMPLE = 3 * 1152 * 4  # three embedding rows, nnet.c:48
 
 def measured_pmc(config, kernel_name):
     """PMC record (tools/pmc_summary.py) of `kernel_name` in bench configuration
-    `config` from the passes of THIS source tree: gpurun_out/ first (a pass
-    just made on this box), then the committed profiles/r*/ (newest round
-    first).  ({}, None) when no record matches the source hash."""
+    `config` from the passes of THIS source tree: bench_out/ first (a pass
+    just made by tools/gpu_evidence.sh), then the committed profiles/r*/
+    (newest round first).  ({}, None) when no record matches the source hash."""
     from pmc_summary import source_sha256
     want = source_sha256(ROOT)
-    cands = [os.path.join(ROOT, "gpurun_out", "pmc_traffic.json")]
+    cands = [os.path.join(ROOT, "bench_out", "pmc_traffic.json")]
     cands += sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_traffic.json")), reverse=True)
     for f in cands:
         try:
@@ -94,11 +102,19 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--preheat-ms", type=float, default=100.0,
                    help="untimed load before the warmup (DPM clock ramp), then every stream is reset")
+    p.add_argument("--full", action="store_true",
+                   help="also run every side measurement (the --no-* switches and --live-only select among them); "
+                        "without it only the headline is measured")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the PCM of the last timed frame to DIR/pcm.npy (float32 [streams][160])")
     p.add_argument("--detail", default=None,
-                   help="side file for the full record (default gpurun_out/bench_detail.json)")
+                   help="side file for the full record (default with --full: bench_out/bench_detail.json)")
     p.add_argument("--timers", type=int, default=1,
                    help="HIP events in the timed region: 0 none, 1 around the sample kernel, 2 both kernels")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def dist_setup(args):
@@ -139,16 +155,43 @@ def max_over_ranks(dist, x):
     return float(t.item())
 
 
+def batch_features(L, stream_base, B, F):
+    """[F][B][20] float32: the synthetic features of streams stream_base ..
+    stream_base + B - 1 (each stream's generator is sequential in its frames
+    and independent of the others: a few worker threads share the streams of
+    a long run, the C generator runs without the GIL)."""
+    feats = np.empty((F, B, 20), np.float32)
+
+    def fill(s):
+        feats[:, s, :] = L.synthetic_features(stream_base + s, F)[:, :20]
+
+    share = int(os.environ.get("OMP_NUM_THREADS", "0") or 0)
+    workers = min(16, len(os.sched_getaffinity(0)), share if share > 0 else 16)
+    if workers <= 1 or F * B < 1 << 16:
+        for s in range(B):
+            fill(s)
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(workers) as ex:
+            list(ex.map(fill, range(B)))
+    return feats
+
+
+PREHEAT_CALL_FRAMES = 256  # longest preheat call: 8 chunks of the chunked frame network
+
+
 def run_batch(L, blob, B, stream_base, warmup, steps, timed_dist=None, timers=1, preheat_ms=0.0, kernel=0,
-              rcp_table=None):
+              rcp_table=None, frame_pass=True, last_only=False):
     """Returns (seconds for `steps` frames, kernel ms / launches, info, pcm).
     The timed region carries HIP events around each sample-kernel launch
     (timers=1; 2 adds the frame kernel); the frame kernel's own time comes
-    from a short untimed pass with both kernels timed."""
+    from a short untimed pass with both kernels timed (frame_pass; without
+    it that figure is 0).  pcm: every frame [warmup + steps][B][160], or with
+    last_only the last timed frame alone [1][B][160] (a long run's PCM is
+    gigabytes)."""
     F = warmup + steps
-    extra = min(steps, 32)  # one chunk of the chunked frame network (B > 128)
-    feats = np.stack([L.synthetic_features(stream_base + s, F)[:, :20] for s in range(B)], 1)
-    feats = np.ascontiguousarray(feats, np.float32)  # [F][B][20]
+    extra = min(steps, 32) if frame_pass else 0  # one chunk of the chunked frame network (B > 128)
+    feats = batch_features(L, stream_base, B, F)  # [F][B][20]
     ndev = max(1, L.device_count())
     b = L.LPCNetBatch(B, int(os.environ.get("LOCAL_RANK", "0")) % ndev, blob)
     if kernel:
@@ -164,10 +207,13 @@ def run_batch(L, blob, B, stream_base, warmup, steps, timed_dist=None, timers=1,
         # the warmup and timed frames below compute exactly what they would
         # without the preheat (same PCM)
         # (calls of `steps` frames: the same multi-frame launches as the
-        # timed call, so a kernel trace of the run averages one population)
+        # timed call, so a kernel trace of the run averages one population;
+        # a long run's calls stop at PREHEAT_CALL_FRAMES, whole chunks like
+        # the bulk of its timed call, so the preheat does not grow with it)
+        pre = min(steps, PREHEAT_CALL_FRAMES)
         t_end = time.perf_counter() + preheat_ms * 1e-3
         while time.perf_counter() < t_end:
-            b.synthesize_frames(None, d_feat, d_pcm, steps)
+            b.synthesize_frames(None, d_feat, d_pcm, pre)
             b.sync()
         b.reset()
     if warmup:
@@ -180,12 +226,18 @@ def run_batch(L, blob, B, stream_base, warmup, steps, timed_dist=None, timers=1,
     dt = time.perf_counter() - t0
     ks, kn = b.kernel_ms(0)
     kf = b.kernel_frames(0)
-    pcm = np.zeros((F, B, 160), np.int16)
-    b.d2h(pcm, d_pcm)
-    b.reset_timers(2)
-    b.synthesize_frames(None, d_feat + warmup * B * 20 * 4, d_pcm + F * B * 160 * 2, extra)
-    b.sync()
-    fs, fn = b.kernel_ms(1)
+    if last_only:
+        pcm = np.zeros((1, B, 160), np.int16)
+        b.d2h(pcm, d_pcm + (F - 1) * B * 160 * 2)
+    else:
+        pcm = np.zeros((F, B, 160), np.int16)
+        b.d2h(pcm, d_pcm)
+    fs, fn = 0.0, 0
+    if frame_pass:
+        b.reset_timers(2)
+        b.synthesize_frames(None, d_feat + warmup * B * 20 * 4, d_pcm + F * B * 160 * 2, extra)
+        b.sync()
+        fs, fn = b.kernel_ms(1)
     info = b.info()
     b.device_free(d_feat)
     b.device_free(d_pcm)
@@ -551,6 +603,15 @@ def run_live(L, blob, B, warmup, steps, preheat_ms=0.0, engine_buffers=True, dis
     return np.array(per), pcm
 
 
+def dump_outputs(outdir, pcm, rank=0, world=1):
+    """--dump-outputs: the PCM of the last timed frame, [streams][160] (int16
+    values, exact in float32), as outdir/pcm.npy (pcm_rank<r>.npy for each
+    rank of a multi-process run)."""
+    os.makedirs(outdir, exist_ok=True)
+    name = "pcm.npy" if world == 1 else f"pcm_rank{rank}.npy"
+    np.save(os.path.join(outdir, name), np.ascontiguousarray(pcm, np.float32))
+
+
 def _json_scalar(o):
     """numpy scalars (np.bool_, np.float64 ...) in the line as their Python values"""
     if isinstance(o, np.generic):
@@ -831,15 +892,19 @@ def main():
     rank0 = int(os.environ.get("RANK", "0")) == 0
     # the drop-in real-time check runs as a child process, before this
     # process initialises the GPU
-    drt = dropin_rt() if rank0 and world == 1 and not (args.no_batch1 or args.live_only or args.no_dropin) else None
+    drt = (dropin_rt() if args.full and rank0 and world == 1 and not (args.no_batch1 or args.live_only or args.no_dropin)
+           else None)
     world, rank, local, dist = dist_setup(args)
     import lpcnet_amd as L
     variant = L.VARIANT_INT8 if args.variant == "int8" else L.VARIANT_FP32
     blob = L.synthetic_model(1, variant)
     B = args.streams
     from lpcnet_amd.shard import weak_shard
+    # a plain run: no frame-kernel pass, only the last frame's PCM copied back
     dt, (ks, kn, kf, fs, fn), info, pcm = run_batch(L, blob, B, weak_shard(rank, B).start, args.warmup, args.steps, dist,
-                                                args.timers, args.preheat_ms)
+                                                args.timers, args.preheat_ms, frame_pass=args.full, last_only=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pcm[-1], rank, world)
     dt = max_over_ranks(dist, dt)
     samples = world * B * 160 * args.steps
     value = samples / dt
@@ -867,7 +932,7 @@ def main():
         "rt_streams_per_gpu": value / world / 16000.0,
         "frame_step_ms": dt / args.steps * 1e3,
         "roofline": rf,
-        "frame_network_ms_per_frame": fs,
+        "frame_network_ms_per_frame": fs if args.full else None,
         # matrix-core work of the sample kernel (north_star: MFMA at batch >= 256):
         # int8 ops issued per launch / launch time, and the PMC busy fraction
         "mfma": mf,
@@ -875,9 +940,10 @@ def main():
                           "lds_bytes": info.lds_bytes, "gru_a_blocks": info.gru_a_blocks},
         "pcm_checksum": int(np.abs(pcm[-1].astype(np.int64)).sum()),
     }
-    if rank == 0 and world == 1 and not args.no_latency:
+    side = args.full and rank == 0 and world == 1  # the side measurements: --full, single process
+    if side and not args.no_latency:
         out["latency"] = latency(L, blob, B, sample_ms)
-    if rank == 0 and world == 1 and not args.no_batch1:
+    if side and not args.no_batch1:
         out["batch1"] = side_line(L, blob, 1, args, "b1", "int8")
         # BASELINE configs[1]: batch=1 with the fp32 (--disable-dot-product) GRU_A weights
         out["batch1_fp32"] = side_line(L, L.synthetic_model(1, L.VARIANT_FP32), 1, args, "b1_fp32", "fp32")
@@ -885,38 +951,39 @@ def main():
         out["batch256"] = side_line(L, blob, 256, args, "b256", "int8")
         # the wide-batch kernel (mfw_kernel) that carries the capacity figures
         out["batch8192"] = side_line(L, blob, 8192, args, "b8192", "int8")
-    if rank == 0 and world == 1 and not args.no_batch1:
+    if side and not args.no_batch1:
         out["skewed_int8"] = skewed_lines(L, args)
         out["lockstep"] = lockstep_lines(L, args)
         out["host_rcpps"] = host_rcpps_lines(L, args)
-    if rank == 0 and world == 1 and (not args.no_batch1 or args.live_only):
+    if side and (not args.no_batch1 or args.live_only):
         # the same workload as a live server runs it: host I/O every frame
         out["live"] = live_line(L, blob, B, args, value)
-    if rank == 0 and world == 1 and args.live_only:
+    if side and args.live_only:
         out["capacity_live"] = capacity_live(L, blob)
-    if rank == 0 and world == 1 and not args.no_capacity and not args.live_only:
+    if side and not args.no_capacity and not args.live_only:
         out["capacity"] = capacity(L, blob, args)
         out["capacity_live"] = capacity_live(L, blob)
         # the same ladder on the trained-like (Sparsify) sparsity pattern
         out["capacity_skewed"] = capacity(L, L.synthetic_model(1, L.VARIANT_INT8, skewed=True), args)
     if drt is not None:
         out["dropin_rt"] = drt
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if side and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         # beside batch1_fp32 (configs[1]): the reference's fp32 build on the same cores
         out["cpu_baseline_fp32"] = cpu_baseline(args.cpu_seconds, 1)
     if rank == 0:
         # the full record (ladders, latency objects, PMC-derived objects) goes
-        # to a side file; stdout's last line is the compact record the
-        # driver parses
-        detail = args.detail or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(out, f, default=_json_scalar, indent=1)
-        except OSError as e:
-            print(f"bench: detail file not written ({e})", file=sys.stderr)
-            detail = None
+        # to a side file (--full, or wherever --detail says); stdout's last
+        # line is the compact record the driver parses
+        detail = args.detail or (os.path.join(ROOT, "bench_out", "bench_detail.json") if args.full else None)
+        if detail:
+            try:
+                os.makedirs(os.path.dirname(detail) or ".", exist_ok=True)
+                with open(detail, "w") as f:
+                    json.dump(out, f, default=_json_scalar, indent=1)
+            except OSError as e:
+                print(f"bench: detail file not written ({e})", file=sys.stderr)
+                detail = None
         print(json.dumps(compact_line(out, detail and os.path.relpath(detail, ROOT)), default=_json_scalar),
               flush=True)
     if dist is not None:

@@ -80,3 +80,30 @@ def test_dropin_rt_needs_both_pacings(monkeypatch):
     d = bench.dropin_rt(threads=(256, 960), frames=300)
     assert d["max_threads_realtime_p99"] == 256
     assert d["at_max"]["burst"]["latency_ms_p99"] == 12.0
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """--full is off by default (a plain run measures the headline only);
+    --steps really is the number of timed frames, so it must be >= 1."""
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float32_pcm(tmp_path):
+    """--dump-outputs: DIR/pcm.npy holds the frame's int16 PCM exactly, as float32."""
+    import numpy as np
+    pcm = (np.arange(3 * 160, dtype=np.int64).reshape(3, 160) * 137 % 65536 - 32768).astype(np.int16)
+    bench.dump_outputs(str(tmp_path / "out"), pcm)
+    got = np.load(tmp_path / "out" / "pcm.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 160)
+    assert np.array_equal(got.astype(np.int16), pcm)
+    bench.dump_outputs(str(tmp_path / "out"), pcm, rank=1, world=2)
+    assert (tmp_path / "out" / "pcm_rank1.npy").exists()

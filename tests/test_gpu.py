@@ -749,6 +749,25 @@ def test_bench_preheat_computes_the_same_frames(require_gpu, blobs):
     assert np.abs(cold[3:].astype(np.int64)).sum() > 0
 
 
+def test_bench_plain_run_computes_the_same_last_frame(require_gpu, blobs, tmp_path):
+    """A plain bench.py run (no frame-kernel pass, only the last timed
+    frame's PCM copied back) computes the frame the full path computes, and
+    --dump-outputs stores it exactly (int16 values in float32)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    blob = blobs["streams_int8"]
+    _, (_, _, _, fs, _), _, full = bench.run_batch(L, blob, 64, 0, 3, 6, None, 1, 0.0)
+    _, (_, _, _, fs0, fn0), _, last = bench.run_batch(L, blob, 64, 0, 3, 6, None, 1, 0.0, frame_pass=False,
+                                                      last_only=True)
+    assert full.shape == (9, 64, 160) and last.shape == (1, 64, 160)
+    assert np.array_equal(last[0], full[-1]) and np.abs(last.astype(np.int64)).sum() > 0
+    assert fs > 0 and fs0 == 0 and fn0 == 0
+    bench.dump_outputs(str(tmp_path / "d"), last[-1])
+    got = np.load(tmp_path / "d" / "pcm.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, full[-1].astype(np.float32))
+
+
 @pytest.mark.parametrize("variant,skewed,B", [(0, False, 300), (0, False, 1030), (0, True, 1030), (0, False, 2100),
                                               (1, False, 200)])
 def test_live_single_frame_chunked_matches_oracle(require_gpu, monkeypatch, variant, skewed, B):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One gpurun session: GPU parity tests (optionally a -k selection in $K),
-# smoke, then the bench line.  Every GPU step has its own time limit; the
+# smoke, then the full bench line (bench.py --full).  Every GPU step has its own time limit; the
 # script stops at the first failing step.
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"
@@ -20,6 +20,8 @@ if [ -z "$NOTEST" ]; then
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1 || { echo "smoke rc=$?"; exit 1; }
   tail -1 gpurun_out/smoke_$TAG.log
 fi
+# the bench line with every side measurement, unless BENCH_ARGS says otherwise
+BENCH_ARGS=${BENCH_ARGS---full}
 if [ -z "$NOBENCH" ]; then
   timeout -k 10 420 python -u bench.py --steps $STEPS ${BENCH_ARGS} > gpurun_out/bench_$TAG.log 2>&1 || { echo "bench rc=$?"; tail -20 gpurun_out/bench_$TAG.log; exit 1; }
   tail -c 1500 gpurun_out/bench_$TAG.log; echo
