@@ -92,8 +92,10 @@ LPCNET_EXPORT int lpcnet_batch_set_kernel(LPCNetBatch *b, int mode);
  * each) -- the reference's parser skips records it does not bind -- else
  * the dump defaults (1.0, 2, 0); the environment variables LPCNET_LPC_GAMMA,
  * LPCNET_FEATURES_DELAY and LPCNET_END2END override both at load time.  This
- * setter changes them for the loaded model (until the next load).  Returns
- * -1 without a model or for an unsupported value. */
+ * setter changes them for the loaded model (until the next load; the
+ * register tables that lpcnet_batch_set_kernel / _set_rcp_table may re-plan
+ * are no load: the constants stay).  Returns -1 without a model or for an
+ * unsupported value. */
 LPCNET_EXPORT int lpcnet_batch_set_model_constants(LPCNetBatch *b, float lpc_gamma, int features_delay, int end2end);
 /* lpcnet_reset() on every stream / on one stream. */
 LPCNET_EXPORT void lpcnet_batch_reset(LPCNetBatch *b);

@@ -1079,7 +1079,11 @@ int model_constants(const std::vector<Arr> &L, ModelConst &mc)
   return check_constants(mc);
 }
 
-int load_model(LPCNetBatch *b, const unsigned char *data, int len, bool upload = true)
+/* replan: the batch's own blob again, for new register tables only
+ * (replan_if_needed): what the caller set since the load -- the model
+ * constants, the rcpps table -- stays as it is, whatever the blob's records
+ * and the environment say. */
+int load_model(LPCNetBatch *b, const unsigned char *data, int len, bool upload = true, bool replan = false)
 {
   std::vector<Arr> L;
   if (!data || len <= 0 || !parse_blob(L, data, len)) {
@@ -1132,7 +1136,8 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, bool upload =
    * records), else the dump defaults; LPCNET_LPC_GAMMA /
    * LPCNET_FEATURES_DELAY / LPCNET_END2END override both (drop-in callers) */
   ModelConst mc{1.0f, DEFAULT_FEATURES_DELAY, 0};
-  if (model_constants(L, mc)) return -1;
+  if (replan) mc = b->mc;
+  else if (model_constants(L, mc)) return -1;
   /* the 1.6 kb/s decoder's codebooks (lpcnet_private.h:109-112, generated
    * ceps_codebooks.c in the reference; lpcnet_enc.c:109-119, 709 give their
    * sizes): optional records -- a blob without them (or with mis-sized ones,
@@ -1197,7 +1202,7 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, bool upload =
    * table (11 bits, each entry twice); a custom table stays across reloads,
    * LPCNET_RCP=host selects this host's at load time */
   std::vector<uint32_t> rcp_dev(RCP_ENTRIES);
-  if (b->rcp_custom && (int)b->rcp_dev.size() == RCP_ENTRIES) {
+  if ((b->rcp_custom || replan) && (int)b->rcp_dev.size() == RCP_ENTRIES) {
     rcp_dev = b->rcp_dev;
   } else {
     for (int i = 0; i < RCP_ENTRIES; i++) rcp_dev[i] = kRcpTable[i >> (RCP_TABLE_BITS - 11)] + kRcpBias;
@@ -2341,14 +2346,32 @@ LPCNET_EXPORT int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *d
 
 /* after a change of the kernel mode or the rcpps table: re-plan the register
  * tables when the wide kernel's plan class no longer matches the choice
- * (speed only; the stream states stay) */
+ * (speed only; the stream states, the model constants and the rcpps table
+ * stay: load_model's replan form).  The new tables are built beside the old
+ * ones, which are freed only once the new ones stand: a re-plan that fails
+ * (a device allocation or upload) keeps the previous, correct tables and
+ * their plan class, and the setter succeeds. */
 static int replan_if_needed(LPCNetBatch *b)
 {
   if (!b->have_model || !b->mf_ok || b->blob.empty() || mfw_planned(b, b->cus) == b->plan_wide) return 0;
   if (b->set_device()) return -1;
   (void)hipStreamSynchronize(b->stream);
   const std::vector<unsigned char> blob = b->blob;
-  return load_model(b, blob.data(), (int)blob.size());
+  const bool plan_wide = b->plan_wide;
+  const L2Warm warm = b->ck_warm;
+  std::vector<void *> old;
+  old.swap(b->model_bufs); /* load_model's free_model finds nothing to free */
+  if (load_model(b, blob.data(), (int)blob.size(), true, true) != 0) {
+    /* load_model commits nothing before its last upload succeeded, and has
+     * freed what it had uploaded itself */
+    b->model_bufs.swap(old);
+    b->have_model = true;
+    b->ck_warm = warm;
+    b->plan_wide = plan_wide;
+    return 0;
+  }
+  for (void *p : old) (void)hipFree(p);
+  return 0;
 }
 
 LPCNET_EXPORT int lpcnet_batch_set_kernel(LPCNetBatch *b, int mode)
@@ -2611,6 +2634,13 @@ static bool pcm_store_coalesced(const LPCNetBatch *b)
   return !getenv("LPCNET_NO_DIRECT_PCM") && (b->fp || b->mfw || (b->mf && !b->mf2));  /* mfw batches: mfw or mf_kernel */
 }
 
+/* copy kind of a feature copy to the device: the batch's own feature buffer
+ * is fine-grained VRAM on large-BAR devices (ensure_host_io), not host memory */
+static hipMemcpyKind own_feat_kind(const LPCNetBatch *b, const float *features)
+{
+  return features == b->h_io_feat && b->io_feat_vram ? hipMemcpyDefault : hipMemcpyHostToDevice;
+}
+
 /* one frame for the first nB streams of a batch, host I/O ([nB][NF] in,
  * [nB][N] out) */
 static int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm, int N, int preload,
@@ -2641,7 +2671,7 @@ static int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm
     if (!own_feat) memcpy(b->h_stg_feat, features, sizeof(float) * NF * nB);
     if (!zc_feat)
       HIPCHK(hipMemcpyAsync(b->d_feat, own_feat ? b->h_io_feat : b->h_stg_feat, sizeof(float) * NF * nB,
-                            hipMemcpyHostToDevice, b->stream));
+                            own_feat_kind(b, features), b->stream));
     const bool direct = own_pcm && pcm_store_coalesced(b);
     const bool defer = lpc_deferred(b);
     if (launch_single_frame_chunked(b, nB, zc_feat ? b->d_io_feat : b->d_feat, direct ? b->d_io_pcm : b->d_pcm, N,
@@ -2670,7 +2700,8 @@ static int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm
   /* everything below is ordered after work already queued on b->stream
    * (staged: the caller has queued the features / preload copies already) */
   if (!staged) {
-    HIPCHK(hipMemcpyAsync(b->d_feat, features, sizeof(float) * NF * nB, hipMemcpyHostToDevice, b->stream));
+    /* the batch's own feature buffer may be device memory (host-visible VRAM) */
+    HIPCHK(hipMemcpyAsync(b->d_feat, features, sizeof(float) * NF * nB, own_feat_kind(b, features), b->stream));
     if (preload > 0 && N > 0)
       HIPCHK(hipMemcpyAsync(b->d_pcm, pcm, sizeof(short) * N * nB, hipMemcpyHostToDevice, b->stream));
   }

@@ -168,9 +168,13 @@ class Oracle:
         if not self._st:
             raise ValueError("oracle_create: blob rejected")
         if constants is not None:
-            g, d, e = constants
-            if self._lib.oracle_set_constants(self._st, g, int(d), int(e)) != 0:
-                raise ValueError("oracle_set_constants: unsupported value")
+            self.set_constants(*constants)
+
+    def set_constants(self, lpc_gamma: float, features_delay: int, end2end) -> None:
+        """LPC_GAMMA / FEATURES_DELAY / END2END from the next frame on; the
+        stream's state stays (lpcnet_batch_set_model_constants between frames)."""
+        if self._lib.oracle_set_constants(self._st, lpc_gamma, int(features_delay), int(end2end)) != 0:
+            raise ValueError("oracle_set_constants: unsupported value")
 
     def synthesize(self, features: np.ndarray, n: int = 160, preload: np.ndarray | None = None,
                    trace: bool = False):

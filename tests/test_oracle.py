@@ -172,6 +172,34 @@ def test_oracle_rejects_bad_constants():
             O.Oracle(blob, 0, constants=c)
 
 
+def test_oracle_set_constants_between_frames():
+    """Oracle.set_constants: before frame 0 it is the constructor's
+    `constants` (the golden fixture); between frames the stream's state stays
+    and only later frames change (what tests/test_gpu_reconfigure.py compares
+    lpcnet_batch_set_model_constants with); bad values are refused."""
+    import lpcnet_amd as L
+    G = np.load(os.path.join(O.GOLDEN, "streams_int8_g092_d3.npz"))
+    g, d, e = G["constants"]
+    blob = L.synthetic_model(1, 0)
+    o = O.Oracle(blob, 0)
+    o.set_constants(float(g), int(d), int(e))
+    F = 8
+    feats = G["features"][0, :F]
+    assert np.array_equal(np.stack([o.synthesize(f) for f in feats]), G["pcm"][0, :F])
+    plain = O.synth_stream(blob, feats, 0)
+    sw = O.Oracle(blob, 0)
+    out = []
+    for fr in range(F):
+        if fr == 4:
+            sw.set_constants(0.9, 2, 0)
+        out.append(sw.synthesize(feats[fr]))
+    out = np.stack(out)
+    assert np.array_equal(out[:4], plain[:4]) and sw.frame_count() == F
+    assert all((out[fr] != plain[fr]).any() for fr in range(4, F))
+    with pytest.raises(ValueError):
+        sw.set_constants(1.0, 5, 0)
+
+
 def test_engine_reads_and_validates_constant_records():
     """The engine takes the constants from optional blob records named like
     nnet_data.h's #defines (validated host-side, no GPU), rejects malformed
