@@ -374,6 +374,78 @@ __device__ __forceinline__ void ga_elementwise(float (&st)[S], const float (&e)[
   for (int s = 0; s < S; s++) xa_i[s * MF_XSTR] = (unsigned char)quant_s8_state(st[s]);
 }
 
+/* at most N of this wave's vector-memory loads still outstanding (they
+ * return in issue order).  The gate's rows pass through the statement: no
+ * use of them is moved ahead of the wait (the compiler otherwise hoists the
+ * input sums of all three gates, with their own waits, above it). */
+template <int N>
+__device__ __forceinline__ void ga_arrived(float (&v)[4][3])
+{
+  asm volatile("s_waitcnt vmcnt(%12)"
+               : "+v"(v[0][0]), "+v"(v[0][1]), "+v"(v[0][2]), "+v"(v[1][0]), "+v"(v[1][1]), "+v"(v[1][2]),
+                 "+v"(v[2][0]), "+v"(v[2][1]), "+v"(v[2][2]), "+v"(v[3][0]), "+v"(v[3][1]), "+v"(v[3][2])
+               : "n"(N)
+               : "memory");
+}
+
+/* ga_elementwise in stages, for gathers issued gate-major (r, z, h) and
+ * still in flight on entry: e[k][s][t] is table t's row of stream s for the
+ * k-th gate issued.  Each stage waits for its own gate's 3S rows only and
+ * runs over all S streams: the r and z sigmoids issue under the transfer of
+ * the later gates, and only the h stage (input sums, hpre * r + inh, tanh,
+ * state update, quantise) follows the last byte.  Same arithmetic as
+ * ga_elementwise, term for term.  The conditioning is read before the first
+ * wait.  Stamps (DIAG 2): 10 = the r rows arrived; MF_FINE: 11 / 12 = the r /
+ * z stage done, 13 = the h stage's state update. */
+template <int S, bool FAST, bool HW, int TB = RCP_TABLE_BITS, typename Stamp>
+__device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)[3][S][3], const float *cnd, int tid,
+                                                      const float (&faz)[S], const float (&far)[S],
+                                                      const float (&tz)[S], const float (&tr)[S],
+                                                      const float (&hpre)[S], const uint32_t *rcp,
+                                                      unsigned char *xa_i, bool stamping, Stamp &stamp)
+{
+  static_assert(S == 4, "staged form: four streams per lane (ga_arrived)");
+  (void)stamping;
+  (void)stamp;
+  float c[3][S]; /* z, r, h */
+  for (int g = 0; g < 3; g++)
+    for (int s = 0; s < S; s++) c[g][s] = cnd[(g * NA + tid) * S + s];
+  /* a z / r gate's pre-activation from its rows ev, conditioning cv,
+   * recurrent sum fa and state term t (the exact form: x86's INT_MIN for
+   * out-of-range / NaN seeds and the wrapping add) */
+  auto pre = [](const float (&ev)[3], float cv, float fa, float t) {
+    const float in = ((cv + ev[0]) + ev[1]) + ev[2];
+    return FAST ? (fa + __builtin_rintf((t + in) * kScale)) * kScale1
+                : (float)((int)fa + cvt_rne((t + in) * kScale)) * kScale1;
+  };
+  auto fine = [&](int k, const float(&v)[S]) {
+#ifdef MF_FINE
+    if (stamping) { float g = 0.f; for (int j = 0; j < S; j++) g += v[j]; asm volatile("" ::"v"(g)); stamp(k); }
+#endif
+  };
+  float rv[S], zv[S], hv[S];
+  ga_arrived<6 * S>(e[0]);
+  if (stamping) stamp(10);
+  for (int s = 0; s < S; s++) rv[s] = pre(e[0][s], c[1][s], far[s], tr[s]);
+  sigmoid_x86_fin_n<S, HW, TB>(rv, rcp);
+  fine(11, rv);
+  __builtin_amdgcn_sched_barrier(0);
+  ga_arrived<3 * S>(e[1]);
+  for (int s = 0; s < S; s++) zv[s] = pre(e[1][s], c[0][s], faz[s], tz[s]);
+  sigmoid_x86_fin_n<S, HW, TB>(zv, rcp);
+  fine(12, zv);
+  __builtin_amdgcn_sched_barrier(0);
+  ga_arrived<0>(e[2]);
+  for (int s = 0; s < S; s++) hv[s] = hpre[s] * rv[s] + (((c[2][s] + e[2][s][0]) + e[2][s][1]) + e[2][s][2]);
+  if (FAST)
+    tanh_x86_fin_n<S, HW, TB>(hv, rcp);
+  else
+    tanh_x86_n<S, HW, TB>(hv, rcp);
+  for (int s = 0; s < S; s++) st[s] = zv[s] * st[s] + (1.f - zv[s]) * hv[s];
+  fine(13, st);
+  for (int s = 0; s < S; s++) xa_i[s * MF_XSTR] = (unsigned char)quant_s8_state(st[s]);
+}
+
 /* v_mfma_i32_16x16x64_i8: A (src0) lane l = row l%16, B (src1) lane l =
  * column l%16, the 16 bytes of both = k 16(l/16) + 0..15 (any k permutation
  * common to A and B is the same product); D lane l register i = row

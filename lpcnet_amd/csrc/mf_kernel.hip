@@ -93,6 +93,10 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
   /* GRU_A elementwise: one stream per lane is latency-bound (hardware rcp),
    * 2-4 streams per lane are VALU-bound (LDS table) */
   constexpr bool kHwA = S == 1 && HWR;
+  /* four streams per lane: gate-major gathers and the staged elementwise
+   * step (ga_elementwise_staged); two streams gain nothing from it (same
+   * box, 513 / 768 streams: +0.2 / -0.5 %) and keep the stream-major form */
+  constexpr bool kStaged = S == 4;
   constexpr bool kGbwLds = S == 4;
 
   bool active[S];
@@ -362,8 +366,37 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
         stamp(5);
         {
           /* GRU_A input (nnet.c:484-491): all 9*S gathers in flight at once */
-          float e[S][9];
-          if constexpr (S > 1) {
+          [[maybe_unused]] float e[S][9];     /* [stream][table * 3 + gate] */
+          [[maybe_unused]] float eg[3][S][3]; /* kStaged: [gate in issue order r, z, h][stream][table] */
+          if constexpr (kStaged) {
+            /* gate-major: the r rows of every stream, then the z rows, then
+             * the h rows.  The loads return in issue order, so the staged
+             * elementwise step starts on the first third of the bytes while
+             * the rest is in flight (z is not needed before the state
+             * update: r first).  Every stream's indices are read before the
+             * first gather; table base in SGPRs, row + lane offset in one
+             * 32-bit VGPR (the global_load saddr form, see below). */
+            int4 ixv[S];
+            for (int s = 0; s < S; s++) ixv[s] = *(const int4 *)(ix + s * 4);
+            uint32_t o[S][3];
+            for (int s = 0; s < S; s++) {
+              o[s][0] = (uint32_t)tid * 4u + (uint32_t)ixv[s].x;
+              o[s][1] = (uint32_t)tid * 4u + (uint32_t)ixv[s].y;
+              o[s][2] = (uint32_t)tid * 4u + (uint32_t)ixv[s].z;
+            }
+            const char *b1 = (const char *)A.mf_emb[0], *b2 = (const char *)A.mf_emb[1], *b3 = (const char *)A.mf_emb[2];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+              const uint32_t g = k < 2 ? 1 - k : k; /* table gate of the k-th issued: r, z, h */
+              for (int s = 0; s < S; s++) asm volatile("" : "+v"(o[s][0]), "+v"(o[s][1]), "+v"(o[s][2]));
+              for (int s = 0; s < S; s++) {
+                eg[k][s][0] = *(const float *)(b1 + o[s][0] + g * NA * 4u);
+                eg[k][s][1] = *(const float *)(b2 + o[s][1] + g * NA * 4u);
+                eg[k][s][2] = *(const float *)(b3 + o[s][2] + g * NA * 4u);
+              }
+              __builtin_amdgcn_sched_barrier(0); /* the gates' loads stay in this order */
+            }
+          } else if constexpr (S > 1) {
             /* split form: every stream's indices read before the first
              * gather (one LDS wait instead of one per stream: skewed model at
              * 1024 streams -2.6 %; the unsplit form and mf2_kernel lose
@@ -442,8 +475,9 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
               far[s] = (float)ar[s];
             }
           }
-          if (stamping) {
-            /* diagnostic only: wait for every gather before the stamp */
+          if (stamping && !kStaged) {
+            /* diagnostic only: wait for every gather before the stamp (the
+             * staged form stamps the first gate's arrival itself) */
             float g = 0.f;
             for (int s = 0; s < S; s++)
 #pragma unroll
@@ -451,9 +485,26 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
             asm volatile("" ::"v"(g));
             stamp(10);
           }
+#ifdef MF_ARRIVAL
+          /* diagnostic build: when each third of the gate-major gathers has
+           * arrived, no work in between (stamps 8, 9, 10) */
+          if constexpr (stamping && kStaged) {
+            __builtin_amdgcn_sched_barrier(0);
+            ga_arrived<6 * S>(eg[0]);
+            stamp(8);
+            ga_arrived<3 * S>(eg[1]);
+            stamp(9);
+            ga_arrived<0>(eg[2]);
+          }
+#endif
           /* compute_sparse_gru elementwise (nnet.c:431-447): one uniform
            * branch per sample into straight-line code for all S streams */
-          if (__builtin_amdgcn_readfirstlane((int)fast))
+          if constexpr (kStaged) {
+            if (__builtin_amdgcn_readfirstlane((int)fast))
+              ga_elementwise_staged<S, true, kHwA>(st, eg, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
+            else
+              ga_elementwise_staged<S, false, kHwA>(st, eg, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
+          } else if (__builtin_amdgcn_readfirstlane((int)fast))
             ga_elementwise<S, true, kHwA>(st, e, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
           else
             ga_elementwise<S, false, kHwA>(st, e, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
