@@ -199,7 +199,8 @@ LPCNET_EXPORT int lpcnet_batch_memcpy_d2h(LPCNetBatch *b, void *dst, const void 
 /* Kernel timing (HIP events on the batch's stream, recorded around every
  * launch since the last reset_timers): which = 0 sample-network kernel,
  * 1 frame-network kernel (per-frame frame kernel, or chunk_kernel once per
- * run of frames).  Returns total ms and the number of launches.
+ * run of frames), 2 the PLC predictor (lpcnet_batch_plc_predict*, timed
+ * whenever enable > 0).  Returns total ms and the number of launches.
  * enable: 0 off, 1 events around the sample kernel only, 2 (or more) around
  * both kernels. */
 LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable);
@@ -238,7 +239,12 @@ LPCNET_EXPORT int lpcnet_batch_get_state(LPCNetBatch *b, int stream, float *gru_
  * a global per-gate energy threshold -- over skewed row energies, so block
  * rows run far above the mean length, as in trained models; bit2 = append
  * synthetic 1.6 kb/s decoder codebooks (ceps_codebook1..3 [1024][17],
- * ceps_codebook_diff4 [4096][18]; the other arrays are unchanged).
+ * ceps_codebook_diff4 [4096][18]; the other arrays are unchanged); bit3 =
+ * append the PLC prediction network's records (training_tf2/dump_plc.py) in
+ * the reference's default shape (cond 128, two GRUs of 256 units,
+ * lpcnet_plc.py:94-103), non-saturating; bits 3 and 4 = the same in a small
+ * unequal shape (cond 64, 128 and 64 units); without bit3 the blob is
+ * unchanged.
  * Returns the blob size; writes it if buf != NULL and cap is large enough. */
 LPCNET_EXPORT int lpcnet_mi355x_synthetic_model(unsigned seed, int variant, int flags, unsigned char *buf, int cap);
 /* Synthetic feature frames (NB_TOTAL_FEATURES floats each) for stream `stream`. */
@@ -344,6 +350,41 @@ LPCNET_EXPORT void lpcnet_mi355x_deinit(LPCNetState *st);
  * codebooks in lpcnet_decoder_init; this library has none).  -1 if the blob
  * is rejected or carries no codebooks. */
 LPCNET_EXPORT int lpcnet_mi355x_decoder_load_model(LPCNetDecState *st, const unsigned char *data, int len);
+
+/* ---- PLC prediction network (compute_plc_pred, lpcnet_plc.c:135-145) ------
+ * The network that predicts the features of a lost frame -- plc_dense1 (57 ->
+ * cond, tanh), plc_gru1 and plc_gru2 (compute_gruB), plc_out (-> NB_FEATURES)
+ * and out[19] = min(.5, out[19] + .1) -- for every stream of a batch in one
+ * launch (plc_kernel.hip), bit-identical per stream to the reference's AVX2
+ * DOT_PROD build.  Its records (training_tf2/dump_plc.py: plc_dense1_weights
+ * / _bias, plc_gru{1,2}_weights / _weights_idx / _recurrent_weights / _bias /
+ * _subias, plc_out_weights / _bias) are optional in a blob, like the decoder
+ * codebooks; the dimensions come from the record sizes (cond, units1, units2:
+ * multiples of 64 up to 512).  A blob without usable records synthesises as
+ * ever and these calls return -1 with the reason in
+ * lpcnet_mi355x_last_error: missing or mis-sized records, unsupported
+ * dimensions, an fp32 (LPCNET_VARIANT_FP32) blob, int8 weights in which a
+ * maddubs pair can saturate.  Emulating that saturation (trained PLC models
+ * are clipped against it, lpcnet_plc.py:69-91) and an fp32 predictor are out
+ * of scope.  Each stream's predictor state (plc_gru1_state, plc_gru2_state:
+ * PLCNetState) lives beside its synthesis state, not in it:
+ * lpcnet_batch_state_size and the synthesis snapshots are unchanged;
+ * lpcnet_batch_reset / _reset_stream zero it (lpcnet_plc_reset). */
+/* dims[4] = {57, cond, units1, units2}; -1 (last_error) if the blob has no usable PLC records. Host only. */
+LPCNET_EXPORT int lpcnet_mi355x_plc_dims(const unsigned char *data, int len, int dims[4]);
+LPCNET_EXPORT int lpcnet_batch_plc_info(const LPCNetBatch *b, int dims[4]);
+/* compute_plc_pred for every stream s with active[s] != 0 (active == NULL: all).
+ * in [B][57] (NULL: all-zero input, the concealment call lpcnet_plc.c:161-162);
+ * out [B][NB_FEATURES] (NULL: discard, :158). Inactive streams: state and out row untouched. */
+LPCNET_EXPORT int lpcnet_batch_plc_predict(LPCNetBatch *b, const float *in, float *out, const unsigned char *active);
+/* the same with device pointers, enqueued on the batch's stream (lpcnet_batch_sync waits);
+ * d_out has the [B][NB_FEATURES] layout lpcnet_batch_synthesize_frames reads as d_features */
+LPCNET_EXPORT int lpcnet_batch_plc_predict_device(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active);
+LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int stream /* -1: all */);
+/* PLCNetState copies (plc_copy[], lpcnet_plc.c:217, 233, 305-306, 313-314) */
+LPCNET_EXPORT int lpcnet_batch_plc_state_size(const LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_plc_save_state(LPCNetBatch *b, int stream, void *buf);
+LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, const void *buf);
 
 /* Last error string of this thread. */
 LPCNET_EXPORT const char *lpcnet_mi355x_last_error(void);

@@ -28,6 +28,7 @@ LIB_PATH = os.path.join(_HERE, "liblpcnet_mi355x%s.so" % (
 
 NB_FEATURES = 20
 NB_TOTAL_FEATURES = 36
+PLC_INPUTS = 57  # 2 NB_BANDS Burg cepstrum + NB_FEATURES + the loss flag (lpcnet_plc.c:149)
 FRAME_SIZE = 160
 VARIANT_INT8 = 0
 VARIANT_FP32 = 1
@@ -120,6 +121,15 @@ def _load():
         "lpcnet_batch_reset_signal": (i, [vp, i]),
         "lpcnet_batch_decode": (i, [vp, vp, vp]),
         "lpcnet_batch_decode_frames": (i, [vp, vp, vp, i]),
+        # PLC prediction network (compute_plc_pred, lpcnet_plc.c:135-145)
+        "lpcnet_mi355x_plc_dims": (i, [C.c_char_p, i, vp]),
+        "lpcnet_batch_plc_info": (i, [vp, vp]),
+        "lpcnet_batch_plc_predict": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_plc_predict_device": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_plc_reset": (i, [vp, i]),
+        "lpcnet_batch_plc_state_size": (i, [vp]),
+        "lpcnet_batch_plc_save_state": (i, [vp, i, vp]),
+        "lpcnet_batch_plc_restore_state": (i, [vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -193,16 +203,29 @@ def set_placement(devices) -> None:
 
 
 def synthetic_model(seed: int = 1, variant: int = VARIANT_INT8, saturating: bool = False, skewed: bool = False,
-                    codebooks: bool = False) -> bytes:
+                    codebooks: bool = False, plc: bool = False, plc_small: bool = False) -> bytes:
     """Deterministic synthetic default-size model in the reference blob format.
     skewed: GRU_A masks by a global per-gate threshold over skewed block
     energies (Sparsify, training_tf2/lpcnet.py:140-160): long block rows.
-    codebooks: append the 1.6 kb/s decoder's ceps codebooks (other arrays unchanged)."""
-    flags = (1 if saturating else 0) | (2 if skewed else 0) | (4 if codebooks else 0)
+    codebooks: append the 1.6 kb/s decoder's ceps codebooks (other arrays unchanged).
+    plc: append the PLC prediction network's records in the reference's default
+    shape (cond 128, 256 / 256 units); plc_small: in a small unequal shape
+    (cond 64, 128 / 64 units) instead (other arrays unchanged)."""
+    flags = ((1 if saturating else 0) | (2 if skewed else 0) | (4 if codebooks else 0) |
+             (8 if plc or plc_small else 0) | (16 if plc_small else 0))
     n = lib.lpcnet_mi355x_synthetic_model(seed, variant, flags, None, 0)
     buf = C.create_string_buffer(n)
     lib.lpcnet_mi355x_synthetic_model(seed, variant, flags, buf, n)
     return buf.raw
+
+
+def plc_dims(blob: bytes) -> tuple[int, int, int, int]:
+    """(57, cond, units1, units2) of a blob's PLC prediction network (host only);
+    raises LPCNetError with the reason if the blob has no usable PLC records."""
+    d = (C.c_int * 4)()
+    if lib.lpcnet_mi355x_plc_dims(blob, len(blob), d) != 0:
+        raise LPCNetError(last_error())
+    return tuple(d)
 
 
 def with_model_constants(blob: bytes, lpc_gamma: float | None = None, features_delay: int | None = None,
@@ -547,6 +570,65 @@ class LPCNetBatch:
 
     def restore_state(self, stream: int, state: bytes) -> None:
         if lib.lpcnet_batch_restore_state(self._b, stream, state) != 0:
+            raise LPCNetError(last_error())
+
+    # -- PLC prediction network (compute_plc_pred, lpcnet_plc.c:135-145) ------
+    def plc_info(self) -> tuple[int, int, int, int]:
+        """(57, cond, units1, units2) of the loaded model's predictor."""
+        d = (C.c_int * 4)()
+        if lib.lpcnet_batch_plc_info(self._b, d) != 0:
+            raise LPCNetError(last_error())
+        return tuple(d)
+
+    def plc_predict(self, inputs: np.ndarray | None = None, active: np.ndarray | None = None,
+                    out: np.ndarray | None = None, discard: bool = False) -> np.ndarray | None:
+        """compute_plc_pred on every stream with active[s] != 0 (None: all).
+        inputs [B, 57] (None: the all-zero concealment input); returns
+        [B, 20] features -- rows of inactive streams keep what ``out`` held
+        (zeros without ``out``) -- or None with discard=True."""
+        x = None if inputs is None else np.ascontiguousarray(inputs, np.float32)
+        if x is not None and x.shape != (self.B, PLC_INPUTS):
+            raise ValueError(f"inputs must be [{self.B}, {PLC_INPUTS}]")
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        if a is not None and a.shape != (self.B,):
+            raise ValueError(f"active must be [{self.B}]")
+        o = None
+        if not discard:
+            o = np.zeros((self.B, NB_FEATURES), np.float32) if out is None else out
+            if o.dtype != np.float32 or o.shape != (self.B, NB_FEATURES) or not o.flags.c_contiguous:
+                raise ValueError(f"out must be a contiguous float32 [{self.B}, {NB_FEATURES}]")
+        if lib.lpcnet_batch_plc_predict(self._b, None if x is None else x.ctypes.data,
+                                        None if o is None else o.ctypes.data,
+                                        None if a is None else a.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def plc_predict_device(self, d_in: int | None, d_out: int | None, d_active: int | None = None) -> None:
+        """Enqueue the predictor on device buffers: d_in [B, 57] (None: zeros),
+        d_out [B, 20] (None: discard; the layout synthesize_frames reads as
+        d_features), d_active [B] bytes (None: all).  sync() waits."""
+        if lib.lpcnet_batch_plc_predict_device(self._b, d_in, d_out, d_active) != 0:
+            raise LPCNetError(last_error())
+
+    def plc_reset(self, stream: int | None = None) -> None:
+        """Zero the predictor state of one stream (None: all), as lpcnet_plc_reset does."""
+        if lib.lpcnet_batch_plc_reset(self._b, -1 if stream is None else stream) != 0:
+            raise LPCNetError(last_error())
+
+    def plc_save_state(self, stream: int) -> bytes:
+        """plc_gru1_state | plc_gru2_state of one stream (the PLC's PLCNetState copies)."""
+        n = lib.lpcnet_batch_plc_state_size(self._b)
+        if n < 0:
+            raise LPCNetError(last_error())
+        buf = C.create_string_buffer(n)
+        if lib.lpcnet_batch_plc_save_state(self._b, stream, buf) != 0:
+            raise LPCNetError(last_error())
+        return buf.raw
+
+    def plc_restore_state(self, stream: int, state: bytes) -> None:
+        if len(state) != lib.lpcnet_batch_plc_state_size(self._b):
+            raise LPCNetError(last_error() or "PLC state of the wrong size")
+        if lib.lpcnet_batch_plc_restore_state(self._b, stream, state) != 0:
             raise LPCNetError(last_error())
 
     # -- device-resident path (benchmarks) ---------------------------------

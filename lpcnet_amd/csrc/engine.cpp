@@ -391,13 +391,24 @@ struct LPCNetBatch {
   unsigned char *d_packets = nullptr;
   float *d_dfeat = nullptr;
   short *d_dpcm = nullptr;
+  /* PLC prediction network (plc_kernel.hip): optional blob records, tables in
+   * buffers of their own (a re-plan of the synthesis tables keeps them), each
+   * stream's plc_gru1_state | plc_gru2_state outside StreamState (the
+   * synthesis snapshots keep their size), host-I/O staging */
+  bool plc_ok = false;
+  std::string plc_why = "no model loaded"; /* why the PLC calls refuse this batch */
+  PlcArgs pa{};
+  std::vector<void *> plc_bufs;
+  float *d_plc_state = nullptr;
+  float *d_plc_in = nullptr, *d_plc_out = nullptr;
+  unsigned char *d_plc_act = nullptr;
   /* diagnostics */
   unsigned long long *d_stamps = nullptr;
   /* timing */
   int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
   std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
-  std::vector<hipEvent_t> ev_pairs[2];
-  std::vector<int> ev_frames[2];    /* frames covered by each pair */
+  std::vector<hipEvent_t> ev_pairs[3]; /* sample kernel, frame kernel, PLC predictor */
+  std::vector<int> ev_frames[3];    /* frames covered by each pair */
   std::vector<hipEvent_t> ev_free;
   /* lower bound of every stream's frame_count (lpcnet.c:119) before the next
    * frame: the multi-frame sample launches start where no stream can still
@@ -1925,6 +1936,206 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, bool upload =
   return 0;
 }
 
+/* ---- PLC prediction network (plc_kernel.hip) ---------------------------- */
+/* The records of training_tf2/dump_plc.py:121-250 under the rules of
+ * dense_init, gru_init and find_idx_check (parse_lpcnet_weights.c:90-171);
+ * the dimensions the generated plc_data.h would carry come from the record
+ * sizes.  Optional in a blob: -1 (set_err names the reason) means the PLC
+ * calls refuse the model, never that synthesis does. */
+struct PlcHost {
+  int cond = 0, n[2] = {0, 0};
+  const float *d1_w = nullptr, *d1_b = nullptr, *out_w = nullptr, *out_b = nullptr;
+  std::vector<uint4> g_in[2], g_rec[2];
+  std::vector<int> seed[2];
+};
+
+/* _mm256_cvtps_epi32 on the host: round to nearest even, out of range / NaN -> INT_MIN */
+int host_cvt_rne(float v)
+{
+  if (!(v >= -2147483648.f && v < 2147483648.f)) return INT32_MIN;
+  return (int)nearbyintf(v);
+}
+
+bool plc_dim_ok(int d) { return d >= 64 && d <= PLC_DIM_MAX && d % 64 == 0; }
+
+/* the blob's variant as load_model chooses it (GRU_A weight bytes per block) */
+int blob_variant(const std::vector<Arr> &L)
+{
+  std::vector<std::vector<int>> ga;
+  if (!parse_idx(L, "sparse_gru_a_recurrent_weights_idx", NA, GA_ROWS, ga)) return -1;
+  const Arr *gaw = find(L, "sparse_gru_a_recurrent_weights");
+  const int nba = total_blocks(ga);
+  if (gaw && gaw->size == 32 * nba) return LPCNET_VARIANT_INT8;
+  if (gaw && gaw->size == 32 * nba * 4) return LPCNET_VARIANT_FP32;
+  set_err("sparse_gru_a_recurrent_weights size matches neither int8 nor fp32");
+  return -1;
+}
+
+int plc_parse(const std::vector<Arr> &L, int variant, PlcHost &P, bool tables)
+{
+  static const char *const names[] = {"plc_dense1_weights", "plc_dense1_bias", "plc_gru1_weights", "plc_gru1_weights_idx",
+                                      "plc_gru1_recurrent_weights", "plc_gru1_bias", "plc_gru1_subias", "plc_gru2_weights",
+                                      "plc_gru2_weights_idx", "plc_gru2_recurrent_weights", "plc_gru2_bias",
+                                      "plc_gru2_subias", "plc_out_weights", "plc_out_bias"};
+  bool any = false;
+  for (const char *nm : names) any |= find(L, nm) != nullptr;
+  if (!any) { set_err("PLC: the model blob carries no PLC records (plc_dense1_*, plc_gru1_*, plc_gru2_*, plc_out_*)"); return -1; }
+  for (const char *nm : names)
+    if (!find(L, nm)) { set_err(std::string("PLC: record missing: ") + nm); return -1; }
+  if (variant != LPCNET_VARIANT_INT8) {
+    set_err("PLC: the predictor runs the int8 (DOT_PROD) numerics only; this is an fp32 blob");
+    return -1;
+  }
+  auto sized = [&](const std::string &nm, int bytes) -> const void * {
+    const Arr *a = find(L, nm.c_str());
+    if (!a || a->size != bytes) { set_err("PLC: record mis-sized: " + nm); return nullptr; }
+    return a->data;
+  };
+  const Arr *d1b = find(L, "plc_dense1_bias");
+  if (d1b->size % 4 || !plc_dim_ok(d1b->size / 4)) {
+    set_err("PLC: unsupported plc_dense1 size (a multiple of 64 up to " + std::to_string(PLC_DIM_MAX) + " units)");
+    return -1;
+  }
+  P.cond = d1b->size / 4;
+  P.d1_b = (const float *)d1b->data;
+  /* 57 = 2 NB_BANDS + NB_FEATURES + 1 inputs (lpcnet_plc.c:149) */
+  if (!(P.d1_w = (const float *)sized("plc_dense1_weights", PLC_IN * P.cond * 4))) return -1;
+  int nin = P.cond;
+  for (int k = 0; k < 2; k++) {
+    const std::string nm = k ? "plc_gru2" : "plc_gru1";
+    const Arr *bias = find(L, (nm + "_bias").c_str());
+    if (bias->size % 24 || !plc_dim_ok(bias->size / 24)) {
+      set_err("PLC: unsupported " + nm + " size (a multiple of 64 up to " + std::to_string(PLC_DIM_MAX) + " units)");
+      return -1;
+    }
+    const int n = P.n[k] = bias->size / 24;
+    const float *subias = (const float *)sized(nm + "_subias", 24 * n);
+    if (!subias) return -1;
+    std::vector<std::vector<int>> blocks;
+    if (!parse_idx(L, (nm + "_weights_idx").c_str(), nin, 3 * n, blocks)) { /* gru2: inputs = units1 */
+      set_err("PLC: " + g_err);
+      return -1;
+    }
+    const int8_t *w = (const int8_t *)sized(nm + "_weights", 32 * total_blocks(blocks));
+    const int8_t *rec = (const int8_t *)sized(nm + "_recurrent_weights", 3 * n * n);
+    if (!w || !rec) return -1;
+    for (int b = 0; b < total_blocks(blocks); b++)
+      if (block_may_saturate(w + 32 * b)) { set_err("PLC: " + nm + "_weights: an int8 pair can saturate maddubs (unsupported)"); return -1; }
+    for (int b = 0; b < 3 * n * n / 32; b++)
+      if (block_may_saturate(rec + 32 * b)) {
+        set_err("PLC: " + nm + "_recurrent_weights: an int8 pair can saturate maddubs (unsupported)");
+        return -1;
+      }
+    /* dense [3 n][nin] form of the block-sparse input weights: blocks the idx
+     * leaves out are zero weights, exact in the integer domain (a position
+     * listed twice adds up, as the reference's loop does) */
+    std::vector<int> wi((size_t)3 * n * nin, 0);
+    const int8_t *wp = w;
+    for (size_t rb = 0; rb < blocks.size(); rb++)
+      for (int pos : blocks[rb]) {
+        for (int r = 0; r < 8; r++)
+          for (int c = 0; c < 4; c++) wi[(rb * 8 + r) * nin + pos + c] += wp[r * 4 + c];
+        wp += 32;
+      }
+    for (int v : wi)
+      if (v < -128 || v > 127) { set_err("PLC: " + nm + "_weights_idx lists a block position twice beyond the int8 range"); return -1; }
+    if (tables) {
+      std::vector<int> wr((size_t)3 * n * n);
+      for (int ob = 0; ob < 3 * n / 8; ob++)
+        for (int ib = 0; ib < n / 4; ib++)
+          for (int r = 0; r < 8; r++)
+            for (int c = 0; c < 4; c++) wr[(size_t)(ob * 8 + r) * n + ib * 4 + c] = rec[((size_t)ob * (n / 4) + ib) * 32 + r * 4 + c];
+      /* A tiles of v_mfma_i32_16x16x64_i8 (lpcnet_engine.h PlcArgs) and the seeds */
+      auto tile = [&](const std::vector<int> &W, int K, std::vector<uint4> &out) {
+        const int nk = K / 64;
+        out.resize((size_t)(n / 16) * 3 * nk * 64);
+        for (int ut = 0; ut < n / 16; ut++)
+          for (int g = 0; g < 3; g++)
+            for (int kt = 0; kt < nk; kt++)
+              for (int l = 0; l < 64; l++) {
+                int8_t by[16];
+                const int row = g * n + 16 * ut + l % 16, k0 = 64 * kt + 16 * (l / 16);
+                for (int j = 0; j < 16; j++) by[j] = (int8_t)W[(size_t)row * K + k0 + j];
+                memcpy(&out[(((size_t)ut * 3 + g) * nk + kt) * 64 + l], by, 16);
+              }
+      };
+      tile(wi, nin, P.g_in[k]);
+      tile(wr, n, P.g_rec[k]);
+      P.seed[k].resize(6 * n);
+      const float scale = 128.f * 127.f; /* vec_avx.h:686 */
+      for (int row = 0; row < 3 * n; row++) {
+        int si = 0, sr = 0;
+        for (int j = 0; j < nin; j++) si += wi[(size_t)row * nin + j];
+        for (int j = 0; j < n; j++) sr += wr[(size_t)row * n + j];
+        P.seed[k][row] = (int)((uint32_t)host_cvt_rne(subias[row] * scale) + (uint32_t)(128 * si));
+        P.seed[k][3 * n + row] = (int)((uint32_t)host_cvt_rne(subias[3 * n + row] * scale) + (uint32_t)(128 * sr));
+      }
+    }
+    nin = n;
+  }
+  if (!(P.out_b = (const float *)sized("plc_out_bias", NF * 4))) return -1;
+  if (!(P.out_w = (const float *)sized("plc_out_weights", P.n[1] * NF * 4))) return -1;
+  return 0;
+}
+
+void plc_free(LPCNetBatch *b)
+{
+  for (void *p : b->plc_bufs) (void)hipFree(p);
+  b->plc_bufs.clear();
+  b->d_plc_state = b->d_plc_in = b->d_plc_out = nullptr;
+  b->d_plc_act = nullptr;
+  b->plc_ok = false;
+  b->pa = PlcArgs{};
+}
+
+/* after a successful load_model of the same blob: the PLC tables and the
+ * per-stream predictor state (zero, as lpcnet_plc_init leaves plc_net) */
+void plc_load(LPCNetBatch *b, const unsigned char *data, int len)
+{
+  plc_free(b);
+  std::vector<Arr> L;
+  PlcHost P;
+  if (!parse_blob(L, data, len) || plc_parse(L, b->variant, P, true)) {
+    b->plc_why = g_err;
+    return;
+  }
+  PlcArgs a{};
+  a.nstreams = b->B;
+  a.cond = P.cond;
+  a.n1 = P.n[0];
+  a.n2 = P.n[1];
+  bool ok = true;
+  auto up = [&](const void *src, size_t bytes) -> void * {
+    void *p = nullptr;
+    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
+    b->plc_bufs.push_back(p);
+    if (src ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(p, 0, bytes) != hipSuccess) ok = false;
+    return p;
+  };
+  a.d1_w = (const float *)up(P.d1_w, (size_t)PLC_IN * P.cond * 4);
+  a.d1_b = (const float *)up(P.d1_b, (size_t)P.cond * 4);
+  a.g1_in = (const uint4 *)up(P.g_in[0].data(), P.g_in[0].size() * sizeof(uint4));
+  a.g1_rec = (const uint4 *)up(P.g_rec[0].data(), P.g_rec[0].size() * sizeof(uint4));
+  a.g1_seed = (const int *)up(P.seed[0].data(), P.seed[0].size() * 4);
+  a.g2_in = (const uint4 *)up(P.g_in[1].data(), P.g_in[1].size() * sizeof(uint4));
+  a.g2_rec = (const uint4 *)up(P.g_rec[1].data(), P.g_rec[1].size() * sizeof(uint4));
+  a.g2_seed = (const int *)up(P.seed[1].data(), P.seed[1].size() * 4);
+  a.out_w = (const float *)up(P.out_w, (size_t)P.n[1] * NF * 4);
+  a.out_b = (const float *)up(P.out_b, NF * 4);
+  a.state = b->d_plc_state = (float *)up(nullptr, (size_t)b->B * (a.n1 + a.n2) * 4);
+  b->d_plc_in = (float *)up(nullptr, (size_t)b->B * PLC_IN * 4);
+  b->d_plc_out = (float *)up(nullptr, (size_t)b->B * NF * 4);
+  b->d_plc_act = (unsigned char *)up(nullptr, (size_t)b->B);
+  if (!ok) {
+    plc_free(b);
+    b->plc_why = "PLC: device allocation or upload of the predictor tables failed";
+    return;
+  }
+  b->pa = a;
+  b->plc_ok = true;
+  b->plc_why.clear();
+}
+
 void host_reset_state(StreamState &s)
 {
   memset(&s, 0, sizeof(s));
@@ -2301,6 +2512,7 @@ LPCNET_EXPORT void lpcnet_batch_destroy(LPCNetBatch *b)
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->fstream) (void)hipStreamSynchronize(b->fstream);
   free_model(b);
+  plc_free(b);
   (void)hipFree(b->d_state);
   (void)hipFree(b->d_ck_sync);
   (void)hipFree(b->d_feat);
@@ -2340,7 +2552,13 @@ LPCNET_EXPORT int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *d
   if (b->set_device()) return -1;
   (void)hipStreamSynchronize(b->stream);
   const int rc = load_model(b, data, len);
-  if (rc == 0) b->blob.assign(data, data + len);
+  if (rc == 0) {
+    b->blob.assign(data, data + len);
+    plc_load(b, data, len); /* optional records: a blob without them loads as ever */
+  } else if (!b->have_model) {
+    plc_free(b);
+    b->plc_why = "no model loaded";
+  }
   return rc;
 }
 
@@ -2434,6 +2652,11 @@ LPCNET_EXPORT int lpcnet_batch_reset_stream(LPCNetBatch *b, int stream)
   StreamState s;
   host_reset_state(s);
   HIPCHK(hipMemcpyAsync(&b->d_state[stream], &s, sizeof(s), hipMemcpyHostToDevice, b->stream));
+  /* lpcnet_plc_reset clears plc_net with the synthesis state */
+  if (b->plc_ok) {
+    const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
+    HIPCHK(hipMemsetAsync(b->d_plc_state + (size_t)stream * nt, 0, nt * 4, b->stream));
+  }
   HIPCHK(hipStreamSynchronize(b->stream));
   b->min_fc = std::min(b->min_fc, s.frame_count);
   return 0;
@@ -2446,6 +2669,7 @@ LPCNET_EXPORT void lpcnet_batch_reset(LPCNetBatch *b)
   host_reset_state(v[0]);
   for (int i = 1; i < b->B; i++) v[i] = v[0];
   (void)hipMemcpyAsync(b->d_state, v.data(), sizeof(StreamState) * v.size(), hipMemcpyHostToDevice, b->stream);
+  if (b->plc_ok) (void)hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * (b->pa.n1 + b->pa.n2) * 4, b->stream);
   (void)hipStreamSynchronize(b->stream);
   b->min_fc = v[0].frame_count;
 }
@@ -3050,7 +3274,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
   if (!b) return;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
-  for (int k = 0; k < 2; k++) {
+  for (int k = 0; k < 3; k++) {
     b->ev_pairs[k].clear();
     b->ev_frames[k].clear();
   }
@@ -3063,7 +3287,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
 
 LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *launches)
 {
-  if (!b || which < 0 || which > 1) return -1;
+  if (!b || which < 0 || which > 2) return -1;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
   double tot = 0;
@@ -3078,7 +3302,7 @@ LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *laun
 
 LPCNET_EXPORT int lpcnet_batch_kernel_frames(LPCNetBatch *b, int which)
 {
-  if (!b || which < 0 || which > 1) return -1;
+  if (!b || which < 0 || which > 2) return -1;
   int n = 0;
   for (int k : b->ev_frames[which]) n += k;
   return n;
@@ -3154,6 +3378,138 @@ LPCNET_EXPORT int lpcnet_batch_get_state(LPCNetBatch *b, int stream, float *gru_
   if (gru_a_state) memcpy(gru_a_state, s.gru_a_state, sizeof(s.gru_a_state));
   if (gru_b_state) memcpy(gru_b_state, s.gru_b_state, sizeof(s.gru_b_state));
   if (frame_count) *frame_count = s.frame_count;
+  return 0;
+}
+
+/* ---- PLC prediction network ---------------------------------------------- */
+
+static int plc_ready(const LPCNetBatch *b)
+{
+  if (!b) { set_err("null batch"); return -1; }
+  if (!b->have_model) { set_err("no model loaded"); return -1; }
+  if (!b->plc_ok) { set_err(b->plc_why.empty() ? "PLC: no usable PLC records" : b->plc_why); return -1; }
+  return 0;
+}
+
+/* one predictor launch on the batch's stream (timed as which = 2 when timing is on) */
+static int plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
+{
+  PlcArgs a = b->pa;
+  a.in = d_in;
+  a.out = d_out;
+  a.active = d_active;
+  a.rcp = b->fa.rcp;
+  a.rcp_hw = b->sa.rcp_hw;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (b->timing) {
+    e0 = get_event(b);
+    e1 = get_event(b);
+    if (e0) b->ev_taken.push_back(e0);
+    if (e1) b->ev_taken.push_back(e1);
+    if (!e0 || !e1) { set_err("hipEventCreate failed"); return -1; }
+    HIPCHK(hipEventRecord(e0, b->stream));
+  }
+  if (launch_plc(a, b->stream)) { set_err("plc kernel launch failed"); return -1; }
+  if (e1) {
+    HIPCHK(hipEventRecord(e1, b->stream));
+    b->ev_pairs[2].push_back(e0);
+    b->ev_pairs[2].push_back(e1);
+    b->ev_frames[2].push_back(1);
+  }
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_mi355x_plc_dims(const unsigned char *data, int len, int dims[4])
+{
+  std::vector<Arr> L;
+  if (!data || len <= 0 || !dims || !parse_blob(L, data, len)) { set_err("malformed weight blob"); return -1; }
+  const int variant = blob_variant(L);
+  if (variant < 0) return -1;
+  PlcHost P;
+  if (plc_parse(L, variant, P, false)) return -1;
+  dims[0] = PLC_IN;
+  dims[1] = P.cond;
+  dims[2] = P.n[0];
+  dims[3] = P.n[1];
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_info(const LPCNetBatch *b, int dims[4])
+{
+  if (plc_ready(b)) return -1;
+  if (!dims) { set_err("bad arguments"); return -1; }
+  dims[0] = PLC_IN;
+  dims[1] = b->pa.cond;
+  dims[2] = b->pa.n1;
+  dims[3] = b->pa.n2;
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_predict_device(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
+{
+  if (plc_ready(b) || b->set_device()) return -1;
+  return plc_launch(b, d_in, d_out, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_predict(LPCNetBatch *b, const float *in, float *out, const unsigned char *active)
+{
+  if (plc_ready(b) || b->set_device()) return -1;
+  const size_t B = (size_t)b->B;
+  if (in) HIPCHK(hipMemcpyAsync(b->d_plc_in, in, B * PLC_IN * 4, hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->d_plc_act, active, B, hipMemcpyHostToDevice, b->stream));
+  if (plc_launch(b, in ? b->d_plc_in : nullptr, out ? b->d_plc_out : nullptr, active ? b->d_plc_act : nullptr)) return -1;
+  if (!out) {
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+  }
+  /* inactive streams keep their out row: the staging rows of the active ones only */
+  std::vector<float> tmp(B * NF);
+  HIPCHK(hipMemcpyAsync(tmp.data(), b->d_plc_out, tmp.size() * 4, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (size_t s = 0; s < B; s++)
+    if (!active || active[s]) memcpy(out + s * NF, &tmp[s * NF], NF * 4);
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int stream)
+{
+  if (plc_ready(b) || b->set_device()) return -1;
+  if (stream < -1 || stream >= b->B) { set_err("no such stream"); return -1; }
+  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
+  if (stream < 0) HIPCHK(hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * nt * 4, b->stream));
+  else HIPCHK(hipMemsetAsync(b->d_plc_state + (size_t)stream * nt, 0, nt * 4, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_state_size(const LPCNetBatch *b)
+{
+  if (plc_ready(b)) return -1;
+  return (b->pa.n1 + b->pa.n2) * 4;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_save_state(LPCNetBatch *b, int stream, void *buf)
+{
+  if (plc_ready(b) || b->set_device()) return -1;
+  if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
+  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(buf, b->d_plc_state + (size_t)stream * nt, nt * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, const void *buf)
+{
+  if (plc_ready(b) || b->set_device()) return -1;
+  if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
+  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
+  /* as snapshot_ok: a GRU state this engine produced lies in [-1, 1] (+ rounding) or is NaN */
+  std::vector<float> v(nt);
+  memcpy(v.data(), buf, nt * 4);
+  for (float x : v)
+    if (x > 2.f || x < -2.f) { set_err("PLC snapshot GRU state outside [-2, 2]: not a state this engine produced"); return -1; }
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(b->d_plc_state + (size_t)stream * nt, buf, nt * 4, hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -440,6 +440,39 @@ struct DecodeArgs {
 constexpr int DEC_MAX_PACKETS = LPC_CHUNK / 4; /* packets per decode launch (the frames of one chunk) */
 int launch_decode(const DecodeArgs &a, void *stream);
 
+/* The PLC prediction network (compute_plc_pred, lpcnet_plc.c:135-145) for a
+ * whole batch (plc_kernel.hip): dense1 57 -> cond (tanh), two compute_gruB
+ * layers cond -> n1 -> n2 (int8, DOT_PROD / USE_SU_BIAS numerics), plc_out
+ * n2 -> NF (linear) and the out[19] boost.  One weight set for every stream;
+ * a workgroup owns PLC_TILE streams, the N of v_mfma_i32_16x16x64_i8.
+ * GRU weights as dense A tiles (the input idx expanded with zero blocks):
+ * [unit tile ut][gate g][k tile kt][64 lanes] uint4, lane l = row g n + 16 ut
+ * + l % 16, bytes k = 64 kt + 16 (l / 16) + 0..15 (mf_common.h mfma16).
+ * seed [2][3 n] int32: rne(subias * SCALE) + 128 * rowsum(w) of the input
+ * half, then of the recurrent half (x is consumed as u8 - 128). */
+constexpr int PLC_IN = 2 * NBANDS + NF + 1; /* Burg cepstrum, features, loss flag */
+constexpr int PLC_TILE = 16;                /* streams per workgroup */
+constexpr int PLC_THREADS = 512;             /* 8 waves: 256 and 1024 measured slower at 8192+ streams (profiles/r08) */
+constexpr int PLC_DIM_MAX = 512;            /* cond, n1, n2: multiples of 64 up to this */
+struct PlcArgs {
+  int nstreams;
+  int cond, n1, n2;
+  const float *in;             /* [B][PLC_IN]; null: all-zero input */
+  float *out;                  /* [B][NF]; null: discarded */
+  const unsigned char *active; /* [B]; null: every stream */
+  float *state;                /* [B][n1 + n2]: plc_gru1_state, plc_gru2_state */
+  const float *d1_w, *d1_b;    /* [PLC_IN][cond], [cond] */
+  const uint4 *g1_in, *g1_rec;
+  const int *g1_seed;
+  const uint4 *g2_in, *g2_rec;
+  const int *g2_seed;
+  const float *out_w, *out_b;  /* [n2][NF], [NF] */
+  const uint32_t *rcp;         /* RCP_ENTRIES-entry table in global memory (the table form) */
+  int rcp_hw;                  /* as SampleArgs::rcp_hw */
+};
+int plc_lds_bytes(int cond, int n1, int n2);
+int launch_plc(const PlcArgs &a, void *stream);
+
 }  // namespace lpcnet_mi355x
 
 #endif

@@ -202,6 +202,41 @@ void emit_sparse(Blob &blob, const Sparse &s, const std::string &wname, const st
   blob.addi(idxname.c_str(), idx);
 }
 
+/* One PLC GRU (dump_plc.py:162-210 dump_gru_layer): block-sparse int8 input
+ * weights + idx, dense recurrent weights in the dotp layout (out_blk, in_blk,
+ * 8, 4), bias [2][3 N] and subias = bias - sum(q) / 128 of each half.  Half
+ * of the input blocks are left out, so the idx is a real one. */
+void emit_plc_gru(Blob &blob, Rng &r, const std::string &name, int nin, int n, int variant)
+{
+  const float dens[3] = {0.5f, 0.5f, 0.5f};
+  Sparse si = make_sparse(r, 3 * n, nin, dens, 0.9f * sqrtf(3.f / (0.5f * nin)), false);
+  std::vector<double> colsum, colsum2(3 * n, 0.0);
+  emit_sparse(blob, si, name + "_weights", name + "_weights_idx", variant, &colsum);
+  std::vector<float> rec = uvec(r, (size_t)n * 3 * n, 0.7f * sqrtf(3.f / n)); /* [in n][out 3 n] */
+  if (variant == LPCNET_VARIANT_INT8) {
+    std::vector<int8_t> q;
+    q.reserve(rec.size());
+    for (int ob = 0; ob < 3 * n / 8; ob++)
+      for (int ib = 0; ib < n / 4; ib++)
+        for (int rr = 0; rr < 8; rr++)
+          for (int c = 0; c < 4; c++) {
+            const int8_t v = q8(rec[(size_t)(ib * 4 + c) * 3 * n + ob * 8 + rr]);
+            q.push_back(v);
+            colsum2[ob * 8 + rr] += v * (1.0 / 128);
+          }
+    blob.add((name + "_recurrent_weights").c_str(), q.data(), (int)q.size());
+  } else {
+    blob.addf((name + "_recurrent_weights").c_str(), rec);
+  }
+  std::vector<float> bias = uvec(r, 6 * n, 0.1f), subias(bias);
+  for (int o = 0; o < 3 * n; o++) {
+    subias[o] = (float)(bias[o] - colsum[o]);
+    subias[3 * n + o] = (float)(bias[3 * n + o] - colsum2[o]);
+  }
+  blob.addf((name + "_bias").c_str(), bias);
+  blob.addf((name + "_subias").c_str(), subias);
+}
+
 }  // namespace
 
 extern "C" LPCNET_EXPORT int lpcnet_mi355x_synthetic_model(unsigned seed, int variant, int flags, unsigned char *buf, int cap)
@@ -307,6 +342,26 @@ extern "C" LPCNET_EXPORT int lpcnet_mi355x_synthetic_model(unsigned seed, int va
     for (int e = 0; e < 4096; e++)
       for (int i = 0; i < 18; i++) d[(size_t)e * 18 + i] = (i == 0 ? 0.5f : 0.25f / i) * c.gauss();
     blob.addf("ceps_codebook_diff4", d);
+  }
+  /* flags bit 3: the PLC prediction network's records (dump_plc.py; the
+   * default shape of lpcnet_plc.py:94-103, cond 128 and two GRUs of 256 units;
+   * with bit 4 a small unequal shape, cond 64, 128 and 64 units), from their
+   * own generator like the codebooks.  Non-saturating (make_sparse's pair
+   * clip; the recurrent amplitudes stay far below it) and scaled so that the
+   * gates' pre-activations are O(1): the GRU states stay inside (-1, 1). */
+  if (flags & 8) {
+    Rng p;
+    p.seed("lpcnet-mi355x-synthetic-plc", seed);
+    const bool small = (flags & 16) != 0;
+    const int pin = 2 * 18 + NB_FEATURES + 1, pc = small ? 64 : 128, n1 = small ? 128 : 256, n2 = small ? 64 : 256;
+    blob.addf("plc_dense1_weights", uvec(p, (size_t)pin * pc, sqrtf(3.f / pin)));
+    blob.addf("plc_dense1_bias", uvec(p, pc, 0.1f));
+    emit_plc_gru(blob, p, "plc_gru1", pc, n1, variant);
+    emit_plc_gru(blob, p, "plc_gru2", n1, n2, variant);
+    blob.addf("plc_out_weights", uvec(p, (size_t)n2 * NB_FEATURES, sqrtf(3.f / n2)));
+    std::vector<float> ob = uvec(p, NB_FEATURES, 0.1f);
+    ob[NB_FEATURES - 1] = 0.3f; /* the out[19] boost's clamp at .5 is met from both sides */
+    blob.addf("plc_out_bias", ob);
   }
   int size = (int)blob.data.size();
   if (buf && cap >= size) memcpy(buf, blob.data.data(), size);
