@@ -149,6 +149,86 @@ __device__ __forceinline__ void sigmoid_x86_n(float (&X)[N], const uint32_t *tab
   for (int k = 0; k < N; k++) X[k] = clamp_x86(__builtin_fmaf(num[k], den[k], 0.5f), 0.f, 1.f);
 }
 
+/* The table forms of the activations below in pieces, so that a caller can
+ * run other work under the table reads' LDS latency.  Front half: the two
+ * Pade polynomials (*_poly_n), then the table reads issued and not pinned
+ * (rcp_issue_n).  Back half: rcp_pin_n waits for the reads, *_back_n is the
+ * exponent fix and the final fma / product and clamp.  poly, issue, pin, back
+ * in a row is the table form of sigmoid_x86_fin_n / tanh_x86_fin_n / tanh_x86_n
+ * below, term for term (those stay as they are: every other kernel's code is
+ * scheduled from them). */
+template <int N>
+__device__ __forceinline__ void sigmoid_x86_poly_n(const float (&X)[N], float (&num)[N], float (&den)[N])
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const float X2 = X[k] * X[k];
+    num[k] = __builtin_fmaf(__builtin_fmaf(0.00950985f, X2, 6.02452230f), X2, 238.13200378f);
+    den[k] = __builtin_fmaf(__builtin_fmaf(0.74287558f, X2, 103.34200287f), X2, 952.72399902f);
+    num[k] = num[k] * X[k];
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void tanh_x86_poly_n(const float (&X)[N], float (&num)[N], float (&den)[N])
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const float X2 = X[k] * X[k];
+    num[k] = __builtin_fmaf(__builtin_fmaf(0.60863042f, X2, 96.39235687f), X2, 952.52801514f);
+    den[k] = __builtin_fmaf(__builtin_fmaf(11.88600922f, X2, 413.36801147f), X2, 952.72399902f);
+    num[k] = num[k] * X[k];
+  }
+}
+
+template <int N, int TB = RCP_TABLE_BITS>
+__device__ __forceinline__ void rcp_issue_n(const float (&den)[N], uint32_t (&t)[N], const uint32_t *tab)
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) t[k] = tab[__builtin_amdgcn_ubfe(__float_as_uint(den[k]), 23 - TB, TB)];
+}
+
+template <int N>
+__device__ __forceinline__ void rcp_pin_n(uint32_t (&t)[N])
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) asm volatile("" : "+v"(t[k]));
+}
+
+/* back halves of the select-free forms (sigmoid_x86_fin_n, tanh_x86_fin_n) */
+template <int N>
+__device__ __forceinline__ void sigmoid_x86_fin_back_n(float (&X)[N], const float (&num)[N], const float (&den)[N],
+                                                       const uint32_t (&t)[N])
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const float r = __int_as_float((int)(t[k] - (__float_as_uint(den[k]) & 0x7f800000u)));
+    X[k] = __builtin_amdgcn_fmed3f(__builtin_fmaf(num[k], r, 0.5f), 0.f, 1.f);
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void tanh_x86_fin_back_n(float (&X)[N], const float (&num)[N], const float (&den)[N],
+                                                    const uint32_t (&t)[N])
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const float r = __int_as_float((int)(t[k] - (__float_as_uint(den[k]) & 0x7f800000u)));
+    X[k] = __builtin_amdgcn_fmed3f(num[k] * r, -1.f, 1.f);
+  }
+}
+
+/* back half of tanh_x86_n's table form: the flush and NaN selects */
+template <int N>
+__device__ __forceinline__ void tanh_x86_back_n(float (&X)[N], const float (&num)[N], float (&den)[N],
+                                                const uint32_t (&t)[N])
+{
+#pragma unroll
+  for (int k = 0; k < N; k++) den[k] = rcp_x86_fix(den[k], t[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) X[k] = clamp_x86(num[k] * den[k], -1.f, 1.f);
+}
+
 /* sigmoid8_approx for inputs of the form (float)(int32) * kScale1 (+ another
  * such term): |X| < 2^18, so X2 < 2^36, the Pade denominator lies in
  * [952.72, 2^73) and the numerator is finite.  rcpps of such a denominator

@@ -391,12 +391,29 @@ __device__ __forceinline__ void ga_arrived(float (&v)[4][3])
 /* ga_elementwise in stages, for gathers issued gate-major (r, z, h) and
  * still in flight on entry: e[k][s][t] is table t's row of stream s for the
  * k-th gate issued.  Each stage waits for its own gate's 3S rows only and
- * runs over all S streams: the r and z sigmoids issue under the transfer of
- * the later gates, and only the h stage (input sums, hpre * r + inh, tanh,
- * state update, quantise) follows the last byte.  Same arithmetic as
- * ga_elementwise, term for term.  The conditioning is read before the first
- * wait.  Stamps (DIAG 2): 10 = the r rows arrived; MF_FINE: 11 / 12 = the r /
- * z stage done, 13 = the h stage's state update. */
+ * runs over all S streams, and each activation's rcpps table reads run under
+ * the next stage's front half (device_math.h: poly + issue | pin + back):
+ *
+ *   r front | z front | r back | h front | z back, zv*st, 1-zv | h back, update
+ *
+ * In the select-free branch the r reads are consumed 74 instructions after
+ * their issue and the h reads 40.  The z reads are awaited after 18 already:
+ * the h conditioning is read from LDS behind them (LDS returns in order), and
+ * its first use two instructions into the h front waits for both.  Reading it
+ * before the first wait instead, so that the z reads last until their own
+ * pin, measured 1.2 % slower at 1024 streams.  Same
+ * arithmetic as ga_elementwise, term for term: only the waits move.  The
+ * fences keep the compiler from sinking a front half below the pin it is
+ * meant to cover.  The z and r conditioning is read before the first wait.
+ * Registers: 253 VGPRs without scratch in the unsplit instances; the split
+ * ones, which also hold the hosted sums' merge, come out 9 registers over
+ * (36 bytes of scratch per lane), taken from values that live across the
+ * whole sample loop (frame staging addresses, activity flags): stored before
+ * it, reloaded once per frame and at the end, nothing inside it.
+ * Stamps (DIAG 2): 10 = the r rows arrived; MF_FINE: 11 = r front, z front
+ * and r back, 12 = h front and z back, 13 = h back and the state update.
+ * (The parent order with stamps around each stage's table reads, the build
+ * behind profiles/r09/exposure_parent.txt: profiles/r09/exposure_build.patch.) */
 template <int S, bool FAST, bool HW, int TB = RCP_TABLE_BITS, typename Stamp>
 __device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)[3][S][3], const float *cnd, int tid,
                                                       const float (&faz)[S], const float (&far)[S],
@@ -405,11 +422,15 @@ __device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)
                                                       unsigned char *xa_i, bool stamping, Stamp &stamp)
 {
   static_assert(S == 4, "staged form: four streams per lane (ga_arrived)");
+  static_assert(!HW, "staged form: the table reciprocal (four streams per lane are VALU-bound)");
   (void)stamping;
   (void)stamp;
   float c[3][S]; /* z, r, h */
-  for (int g = 0; g < 3; g++)
+  for (int g = 0; g < 2; g++)
     for (int s = 0; s < S; s++) c[g][s] = cnd[(g * NA + tid) * S + s];
+  auto h_cond = [&]() {
+    for (int s = 0; s < S; s++) c[2][s] = cnd[(2 * NA + tid) * S + s];
+  };
   /* a z / r gate's pre-activation from its rows ev, conditioning cv,
    * recurrent sum fa and state term t (the exact form: x86's INT_MIN for
    * out-of-range / NaN seeds and the wrapping add) */
@@ -418,30 +439,59 @@ __device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)
     return FAST ? (fa + __builtin_rintf((t + in) * kScale)) * kScale1
                 : (float)((int)fa + cvt_rne((t + in) * kScale)) * kScale1;
   };
-  auto fine = [&](int k, const float(&v)[S]) {
+  auto fine = [&](int k, const auto &v) {
 #ifdef MF_FINE
-    if (stamping) { float g = 0.f; for (int j = 0; j < S; j++) g += v[j]; asm volatile("" ::"v"(g)); stamp(k); }
+    if (stamping) { auto g = v[0]; for (int j = 1; j < S; j++) g += v[j]; asm volatile("" ::"v"(g)); stamp(k); }
 #endif
   };
-  float rv[S], zv[S], hv[S];
+  float rv[S], zv[S], hv[S], zs[S], zc[S];
+  float rn[S], rd[S], zn[S], zd[S], hn[S], hd[S];
+  uint32_t rt[S], zt[S], ht[S];
+  auto h_back = [&]() {
+    rcp_pin_n(ht);
+    if (FAST)
+      tanh_x86_fin_back_n(hv, hn, hd, ht);
+    else
+      tanh_x86_back_n(hv, hn, hd, ht);
+  };
+  /* r front */
   ga_arrived<6 * S>(e[0]);
   if (stamping) stamp(10);
   for (int s = 0; s < S; s++) rv[s] = pre(e[0][s], c[1][s], far[s], tr[s]);
-  sigmoid_x86_fin_n<S, HW, TB>(rv, rcp);
-  fine(11, rv);
+  sigmoid_x86_poly_n(rv, rn, rd);
+  rcp_issue_n<S, TB>(rd, rt, rcp);
   __builtin_amdgcn_sched_barrier(0);
+  /* z front, under the r reads */
   ga_arrived<3 * S>(e[1]);
   for (int s = 0; s < S; s++) zv[s] = pre(e[1][s], c[0][s], faz[s], tz[s]);
-  sigmoid_x86_fin_n<S, HW, TB>(zv, rcp);
-  fine(12, zv);
+  sigmoid_x86_poly_n(zv, zn, zd);
+  rcp_issue_n<S, TB>(zd, zt, rcp);
+  h_cond(); /* behind the z reads: the h front's first use awaits both (see above) */
   __builtin_amdgcn_sched_barrier(0);
+  /* r back */
+  rcp_pin_n(rt);
+  sigmoid_x86_fin_back_n(rv, rn, rd, rt);
+  fine(11, rv);
+  __builtin_amdgcn_sched_barrier(0);
+  /* h front, under the z reads */
   ga_arrived<0>(e[2]);
   for (int s = 0; s < S; s++) hv[s] = hpre[s] * rv[s] + (((c[2][s] + e[2][s][0]) + e[2][s][1]) + e[2][s][2]);
-  if (FAST)
-    tanh_x86_fin_n<S, HW, TB>(hv, rcp);
-  else
-    tanh_x86_n<S, HW, TB>(hv, rcp);
-  for (int s = 0; s < S; s++) st[s] = zv[s] * st[s] + (1.f - zv[s]) * hv[s];
+  tanh_x86_poly_n(hv, hn, hd);
+  rcp_issue_n<S, TB>(hd, ht, rcp);
+  __builtin_amdgcn_sched_barrier(0);
+  /* z back and the state update's terms that need no tanh, under the h reads */
+  rcp_pin_n(zt);
+  sigmoid_x86_fin_back_n(zv, zn, zd, zt);
+  for (int s = 0; s < S; s++) {
+    zs[s] = zv[s] * st[s];
+    zc[s] = 1.f - zv[s];
+  }
+  fine(12, zc);
+  __builtin_amdgcn_sched_barrier(0);
+  /* h back */
+  h_back();
+  /* the state update: zv * st + (1 - zv) * hv, four separately rounded operations */
+  for (int s = 0; s < S; s++) st[s] = zs[s] + zc[s] * hv[s];
   fine(13, st);
   for (int s = 0; s < S; s++) xa_i[s * MF_XSTR] = (unsigned char)quant_s8_state(st[s]);
 }
