@@ -12,10 +12,10 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/rcp_table_x86.inc
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
@@ -76,6 +76,10 @@ $(BUILD)/decode_kernel.o: $(CSRC)/decode_kernel.hip $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
 $(BUILD)/plc_kernel.o: $(CSRC)/plc_kernel.hip $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
+# the flags of lpc_kernel, whose stages it shares (lpc_stages.h)
+$(BUILD)/feat_kernel.o: $(CSRC)/feat_kernel.hip $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
 $(BUILD)/model_gen.o: $(CSRC)/model_gen.cpp $(HDRS) | $(BUILD)

@@ -200,7 +200,9 @@ LPCNET_EXPORT int lpcnet_batch_memcpy_d2h(LPCNetBatch *b, void *dst, const void 
  * launch since the last reset_timers): which = 0 sample-network kernel,
  * 1 frame-network kernel (per-frame frame kernel, or chunk_kernel once per
  * run of frames), 2 the PLC predictor (lpcnet_batch_plc_predict*, timed
- * whenever enable > 0).  Returns total ms and the number of launches.
+ * whenever enable > 0), 3 the feature extractor
+ * (lpcnet_batch_compute_features*, one launch per frame, likewise).  Returns
+ * total ms and the number of launches.
  * enable: 0 off, 1 events around the sample kernel only, 2 (or more) around
  * both kernels. */
 LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable);
@@ -385,6 +387,46 @@ LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int stream /* -1: all *
 LPCNET_EXPORT int lpcnet_batch_plc_state_size(const LPCNetBatch *b);
 LPCNET_EXPORT int lpcnet_batch_plc_save_state(LPCNetBatch *b, int stream, void *buf);
 LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, const void *buf);
+
+/* ---- Feature extraction (lpcnet_compute_single_frame_features) -------------
+ * The analysis side for a whole batch in one launch per frame
+ * (feat_kernel.hip): preemphasis, compute_frame_features and
+ * process_single_frame (lpcnet_enc.c:872-880, 488-577, 814-870, pcount = 0),
+ * what lpcnet_plc_update_causal / _conceal_causal run on every frame
+ * (lpcnet_plc.c:251-254, 322-328), bit-identical per stream to the
+ * reference's build.  A row of NB_TOTAL_FEATURES (36) floats per stream:
+ * [0, 18) the cepstrum, [18] the pitch, [19] the pitch correlation, [20, 36)
+ * the frame's LPC.  The analysis has no weights: these calls need no model
+ * and no call that changes the model or its kernels changes their results.
+ * Each stream's analysis state (the part of LPCNetEncState this path carries)
+ * lives beside its synthesis state, not in it, and is allocated by the first
+ * of these calls: lpcnet_batch_state_size and the synthesis snapshots are
+ * unchanged; lpcnet_batch_reset / _reset_stream zero it (lpcnet_encoder_init
+ * inside lpcnet_plc_reset).
+ * Out of scope: burg_cepstral_analysis, the PLC state machine,
+ * process_superframe / lpcnet_encode / lpcnet_compute_features (the
+ * four-frame quantisation), and drop-in LPCNetEncState handles (one stream
+ * per launch is slower than the CPU).
+ * Argument errors return -1 with the reason in lpcnet_mi355x_last_error. */
+/* lpcnet_compute_single_frame_features for every stream s with active[s] != 0
+ * (NULL: all). pcm [B][160]; features [B][NB_TOTAL_FEATURES]. Inactive streams:
+ * state and output row untouched. */
+LPCNET_EXPORT int lpcnet_batch_compute_features(LPCNetBatch *b, const short *pcm, float *features, const unsigned char *active);
+LPCNET_EXPORT int lpcnet_batch_compute_features_float(LPCNetBatch *b, const float *pcm, float *features,
+                                                      const unsigned char *active);
+/* device pointers, enqueued on the batch's stream (lpcnet_batch_sync waits):
+ * nframes consecutive frames, d_pcm [nframes][B][160] (the layout
+ * lpcnet_batch_synthesize_frames writes), d_features [nframes][B][row] with
+ * row = NB_FEATURES (what synthesize_frames reads as d_features; columns
+ * 36..55 of a plc_predict_device input row hold the same 20 values) or
+ * NB_TOTAL_FEATURES; anything else -1.  d_active [B] applies to every frame. */
+LPCNET_EXPORT int lpcnet_batch_compute_features_device(LPCNetBatch *b, const short *d_pcm, float *d_features, int row,
+                                                       const unsigned char *d_active, int nframes);
+LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream /* -1: all */);
+/* snapshots of one stream's analysis state; the size is the same for every batch (b may be NULL) */
+LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf);
+LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf);
 
 /* Last error string of this thread. */
 LPCNET_EXPORT const char *lpcnet_mi355x_last_error(void);

@@ -130,6 +130,14 @@ def _load():
         "lpcnet_batch_plc_state_size": (i, [vp]),
         "lpcnet_batch_plc_save_state": (i, [vp, i, vp]),
         "lpcnet_batch_plc_restore_state": (i, [vp, i, vp]),
+        # feature extraction (lpcnet_compute_single_frame_features)
+        "lpcnet_batch_compute_features": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_compute_features_float": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_compute_features_device": (i, [vp, vp, vp, i, vp, i]),
+        "lpcnet_batch_features_reset": (i, [vp, i]),
+        "lpcnet_batch_features_state_size": (i, [vp]),
+        "lpcnet_batch_features_save_state": (i, [vp, i, vp]),
+        "lpcnet_batch_features_restore_state": (i, [vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -631,6 +639,57 @@ class LPCNetBatch:
         if lib.lpcnet_batch_plc_restore_state(self._b, stream, state) != 0:
             raise LPCNetError(last_error())
 
+    # -- feature extraction (lpcnet_compute_single_frame_features) ----------
+    def compute_features(self, pcm: np.ndarray, active: np.ndarray | None = None,
+                         out: np.ndarray | None = None) -> np.ndarray:
+        """preemphasis + compute_frame_features + process_single_frame on every
+        stream with active[s] != 0 (None: all).  pcm [B, 160], int16 or float32
+        (the reference's short -> float conversion already done); returns
+        [B, 36] features -- rows of inactive streams keep what ``out`` held
+        (zeros without ``out``).  Needs no model."""
+        p = np.asarray(pcm)
+        if p.dtype not in (np.int16, np.float32):
+            raise ValueError("pcm must be int16 or float32")
+        p = np.ascontiguousarray(p)
+        if p.shape != (self.B, FRAME_SIZE):
+            raise ValueError(f"pcm must be [{self.B}, {FRAME_SIZE}]")
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        if a is not None and a.shape != (self.B,):
+            raise ValueError(f"active must be [{self.B}]")
+        o = np.zeros((self.B, NB_TOTAL_FEATURES), np.float32) if out is None else out
+        if o.dtype != np.float32 or o.shape != (self.B, NB_TOTAL_FEATURES) or not o.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous float32 [{self.B}, {NB_TOTAL_FEATURES}]")
+        fn = lib.lpcnet_batch_compute_features if p.dtype == np.int16 else lib.lpcnet_batch_compute_features_float
+        if fn(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def compute_features_device(self, d_pcm: int, d_features: int, row: int = NB_FEATURES,
+                                d_active: int | None = None, nframes: int = 1) -> None:
+        """Enqueue the extractor on device buffers: d_pcm [nframes, B, 160] int16
+        (what synthesize_frames writes), d_features [nframes, B, row] with row
+        20 (what synthesize_frames reads as d_features) or 36,
+        d_active [B] bytes (None: all).  sync() waits."""
+        if lib.lpcnet_batch_compute_features_device(self._b, d_pcm, d_features, row, d_active, nframes) != 0:
+            raise LPCNetError(last_error())
+
+    def features_reset(self, stream: int | None = None) -> None:
+        """Zero the analysis state of one stream (None: all), as lpcnet_encoder_init does."""
+        if lib.lpcnet_batch_features_reset(self._b, -1 if stream is None else stream) != 0:
+            raise LPCNetError(last_error())
+
+    def features_save_state(self, stream: int) -> bytes:
+        buf = C.create_string_buffer(lib.lpcnet_batch_features_state_size(self._b))
+        if lib.lpcnet_batch_features_save_state(self._b, stream, buf) != 0:
+            raise LPCNetError(last_error())
+        return buf.raw
+
+    def features_restore_state(self, stream: int, state: bytes) -> None:
+        if len(state) != lib.lpcnet_batch_features_state_size(self._b):
+            raise LPCNetError("analysis state of the wrong size")
+        if lib.lpcnet_batch_features_restore_state(self._b, stream, state) != 0:
+            raise LPCNetError(last_error())
+
     # -- device-resident path (benchmarks) ---------------------------------
     def device_alloc(self, nbytes: int) -> int:
         p = lib.lpcnet_batch_device_alloc(self._b, nbytes)
@@ -666,7 +725,8 @@ class LPCNetBatch:
         lib.lpcnet_batch_reset_timers(self._b, 2 if enable is True else int(enable))
 
     def kernel_ms(self, which: int = 0) -> tuple[float, int]:
-        """(total ms, launches) of the timed launches since reset_timers."""
+        """(total ms, launches) of the timed launches since reset_timers: which = 0 sample
+        kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor."""
         n = C.c_int(0)
         ms = lib.lpcnet_batch_kernel_ms(self._b, which, C.byref(n))
         return ms, n.value

@@ -266,6 +266,23 @@ void build_lpc_tables(LpcTables &T)
   T.scale = 1.f / 320.f;
 }
 
+/* ---- feature extractor tables (feat_kernel.hip) --------------------------- */
+/* half_window as dump_lpcnet_tables.c:83-84 computes it (double, rounded to
+ * float; lpcnet_tables.c prints it with nine digits, which round-trip), and
+ * lpcn_compute_band_energy's (float)j/band_size of every bin (freq.c:138-141). */
+void build_feat_tables(FeatTables &T)
+{
+  static const short eband[LPC_NBANDS] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};
+  memset(&T, 0, sizeof(T));
+  for (int i = 0; i < FRAME; i++)
+    T.half_window[i] = (float)sin(.5 * M_PI * sin(.5 * M_PI * (i + .5) / FRAME) * sin(.5 * M_PI * (i + .5) / FRAME));
+  for (int b = 0; b < LPC_NBANDS; b++) T.band_start[b] = eband[b] * 4;
+  for (int b = 0; b < LPC_NBANDS - 1; b++) {
+    const int n = (eband[b + 1] - eband[b]) * 4;
+    for (int j = 0; j < n; j++) T.frac[eband[b] * 4 + j] = (float)j / n;
+  }
+}
+
 }  // namespace
 
 /* ---- launcher helpers (lpcnet_engine.h), keyed by the current device ---- */
@@ -402,13 +419,22 @@ struct LPCNetBatch {
   float *d_plc_state = nullptr;
   float *d_plc_in = nullptr, *d_plc_out = nullptr;
   unsigned char *d_plc_act = nullptr;
+  /* feature extractor (feat_kernel.hip): no weights, so nothing here depends
+   * on the model; each stream's analysis state in an array of its own, the
+   * constant tables and the host-I/O staging, all allocated by the first
+   * call that extracts features (feat_ensure) */
+  FeatState *d_feat_state = nullptr;
+  FeatTables *d_feat_tab = nullptr;
+  float *d_feat_pcm = nullptr;  /* [B][FRAME] float or short */
+  float *d_feat_out = nullptr;  /* [B][NTF] */
+  unsigned char *d_feat_act = nullptr;
   /* diagnostics */
   unsigned long long *d_stamps = nullptr;
   /* timing */
   int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
   std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
-  std::vector<hipEvent_t> ev_pairs[3]; /* sample kernel, frame kernel, PLC predictor */
-  std::vector<int> ev_frames[3];    /* frames covered by each pair */
+  std::vector<hipEvent_t> ev_pairs[4]; /* sample kernel, frame kernel, PLC predictor, feature extractor */
+  std::vector<int> ev_frames[4];    /* frames covered by each pair */
   std::vector<hipEvent_t> ev_free;
   /* lower bound of every stream's frame_count (lpcnet.c:119) before the next
    * frame: the multi-frame sample launches start where no stream can still
@@ -2513,6 +2539,11 @@ LPCNET_EXPORT void lpcnet_batch_destroy(LPCNetBatch *b)
   if (b->fstream) (void)hipStreamSynchronize(b->fstream);
   free_model(b);
   plc_free(b);
+  (void)hipFree(b->d_feat_state);
+  (void)hipFree(b->d_feat_tab);
+  (void)hipFree(b->d_feat_pcm);
+  (void)hipFree(b->d_feat_out);
+  (void)hipFree(b->d_feat_act);
   (void)hipFree(b->d_state);
   (void)hipFree(b->d_ck_sync);
   (void)hipFree(b->d_feat);
@@ -2657,6 +2688,8 @@ LPCNET_EXPORT int lpcnet_batch_reset_stream(LPCNetBatch *b, int stream)
     const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
     HIPCHK(hipMemsetAsync(b->d_plc_state + (size_t)stream * nt, 0, nt * 4, b->stream));
   }
+  /* and the analysis state (lpcnet_encoder_init inside lpcnet_plc_reset) */
+  if (b->d_feat_state) HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   b->min_fc = std::min(b->min_fc, s.frame_count);
   return 0;
@@ -2670,6 +2703,7 @@ LPCNET_EXPORT void lpcnet_batch_reset(LPCNetBatch *b)
   for (int i = 1; i < b->B; i++) v[i] = v[0];
   (void)hipMemcpyAsync(b->d_state, v.data(), sizeof(StreamState) * v.size(), hipMemcpyHostToDevice, b->stream);
   if (b->plc_ok) (void)hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * (b->pa.n1 + b->pa.n2) * 4, b->stream);
+  if (b->d_feat_state) (void)hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream);
   (void)hipStreamSynchronize(b->stream);
   b->min_fc = v[0].frame_count;
 }
@@ -3274,7 +3308,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
   if (!b) return;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
-  for (int k = 0; k < 3; k++) {
+  for (int k = 0; k < 4; k++) {
     b->ev_pairs[k].clear();
     b->ev_frames[k].clear();
   }
@@ -3287,7 +3321,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
 
 LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *launches)
 {
-  if (!b || which < 0 || which > 2) return -1;
+  if (!b || which < 0 || which > 3) return -1;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
   double tot = 0;
@@ -3302,7 +3336,7 @@ LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *laun
 
 LPCNET_EXPORT int lpcnet_batch_kernel_frames(LPCNetBatch *b, int which)
 {
-  if (!b || which < 0 || which > 2) return -1;
+  if (!b || which < 0 || which > 3) return -1;
   int n = 0;
   for (int k : b->ev_frames[which]) n += k;
   return n;
@@ -3510,6 +3544,160 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
     if (x > 2.f || x < -2.f) { set_err("PLC snapshot GRU state outside [-2, 2]: not a state this engine produced"); return -1; }
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipMemcpy(b->d_plc_state + (size_t)stream * nt, buf, nt * 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
+/* ---- feature extractor (lpcnet_compute_single_frame_features) ------------- */
+
+/* the analysis state, tables and staging of a batch, on its first extraction */
+static int feat_ensure(LPCNetBatch *b)
+{
+  if (b->d_feat_state) return 0;
+  const size_t B = (size_t)b->B;
+  FeatTables T;
+  build_feat_tables(T);
+  FeatState *st = nullptr;
+  FeatTables *tab = nullptr;
+  float *pcm = nullptr, *out = nullptr;
+  unsigned char *act = nullptr;
+  const bool ok = hipMalloc(&st, sizeof(FeatState) * B) == hipSuccess &&
+                  hipMemsetAsync(st, 0, sizeof(FeatState) * B, b->stream) == hipSuccess && /* ordered before the first launch */
+                  hipMalloc(&tab, sizeof(T)) == hipSuccess && hipMemcpy(tab, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMalloc(&pcm, B * FRAME * 4) == hipSuccess && hipMalloc(&out, B * NTF * 4) == hipSuccess &&
+                  hipMalloc(&act, B) == hipSuccess;
+  if (!ok) {
+    (void)hipFree(st);
+    (void)hipFree(tab);
+    (void)hipFree(pcm);
+    (void)hipFree(out);
+    (void)hipFree(act);
+    set_err("features: device allocation failed");
+    return -1;
+  }
+  b->d_feat_state = st;
+  b->d_feat_tab = tab;
+  b->d_feat_pcm = pcm;
+  b->d_feat_out = out;
+  b->d_feat_act = act;
+  return 0;
+}
+
+/* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
+static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
+                       const unsigned char *d_active)
+{
+  FeatArgs a{};
+  a.nstreams = b->B;
+  a.pcm = d_pcm;
+  a.pcm_f = d_pcm_f;
+  a.features = d_features;
+  a.row = row;
+  a.active = d_active;
+  a.state = b->d_feat_state;
+  a.lpc_tab = b->d_lpc_tab;
+  a.tab = b->d_feat_tab;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (b->timing) {
+    e0 = get_event(b);
+    e1 = get_event(b);
+    if (e0) b->ev_taken.push_back(e0);
+    if (e1) b->ev_taken.push_back(e1);
+    if (!e0 || !e1) { set_err("hipEventCreate failed"); return -1; }
+    HIPCHK(hipEventRecord(e0, b->stream));
+  }
+  if (launch_feat(a, b->stream)) { set_err("feature kernel launch failed"); return -1; }
+  if (e1) {
+    HIPCHK(hipEventRecord(e1, b->stream));
+    b->ev_pairs[3].push_back(e0);
+    b->ev_pairs[3].push_back(e1);
+    b->ev_frames[3].push_back(1);
+  }
+  return 0;
+}
+
+static int feat_host(LPCNetBatch *b, const void *pcm, bool is_float, float *features, const unsigned char *active)
+{
+  if (!pcm || !features) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (b->set_device() || feat_ensure(b)) return -1;
+  const size_t B = (size_t)b->B;
+  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * (is_float ? 4 : 2), hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
+  if (feat_launch(b, is_float ? nullptr : (const short *)b->d_feat_pcm, is_float ? b->d_feat_pcm : nullptr, b->d_feat_out, NTF,
+                  active ? b->d_feat_act : nullptr))
+    return -1;
+  /* inactive streams keep their row: the staging rows of the active ones only */
+  std::vector<float> tmp(B * NTF);
+  HIPCHK(hipMemcpyAsync(tmp.data(), b->d_feat_out, tmp.size() * 4, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (size_t s = 0; s < B; s++)
+    if (!active || active[s]) memcpy(features + s * NTF, &tmp[s * NTF], NTF * 4);
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_compute_features(LPCNetBatch *b, const short *pcm, float *features, const unsigned char *active)
+{
+  return feat_host(b, pcm, false, features, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_compute_features_float(LPCNetBatch *b, const float *pcm, float *features,
+                                                      const unsigned char *active)
+{
+  return feat_host(b, pcm, true, features, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_compute_features_device(LPCNetBatch *b, const short *d_pcm, float *d_features, int row,
+                                                       const unsigned char *d_active, int nframes)
+{
+  if (row != NF && row != NTF) { set_err("features: row must be NB_FEATURES (20) or NB_TOTAL_FEATURES (36)"); return -1; }
+  if (nframes < 0) { set_err("features: nframes < 0"); return -1; }
+  if (!d_pcm || !d_features) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (b->set_device() || feat_ensure(b)) return -1;
+  /* the frames of a stream are sequential: one launch per frame, in stream order */
+  for (int f = 0; f < nframes; f++)
+    if (feat_launch(b, d_pcm + (size_t)f * b->B * FRAME, nullptr, d_features + (size_t)f * b->B * row, row, d_active)) return -1;
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream)
+{
+  if (stream < -1) { set_err("no such stream"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (stream >= b->B) { set_err("no such stream"); return -1; }
+  if (!b->d_feat_state) return 0; /* never used: a first use starts from the reset state */
+  if (b->set_device()) return -1;
+  if (stream < 0) HIPCHK(hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream));
+  else HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *) { return (int)sizeof(FeatState); }
+
+LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf)
+{
+  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (stream >= b->B) { set_err("no such stream"); return -1; }
+  if (b->set_device() || feat_ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(buf, b->d_feat_state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf)
+{
+  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
+  /* the kernel indexes its Viterbi rows with best_i */
+  FeatState s;
+  memcpy(&s, buf, sizeof(s));
+  if (s.best_i < 0 || s.best_i >= PITCH_STATES) { set_err("features snapshot: best_i outside [0, 224): not a state this engine produced"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (stream >= b->B) { set_err("no such stream"); return -1; }
+  if (b->set_device() || feat_ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(b->d_feat_state + stream, &s, sizeof(s), hipMemcpyHostToDevice));
   return 0;
 }
 

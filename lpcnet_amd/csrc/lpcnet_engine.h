@@ -473,6 +473,44 @@ struct PlcArgs {
 int plc_lds_bytes(int cond, int n1, int n2);
 int launch_plc(const PlcArgs &a, void *stream);
 
+/* The single-frame feature extractor (preemphasis, compute_frame_features,
+ * process_single_frame: lpcnet_enc.c:872-880, 488-577, 814-870, pcount = 0)
+ * for a whole batch (feat_kernel.hip).  What of LPCNetEncState crosses frames
+ * on that path, per stream, outside StreamState (the synthesis snapshots keep
+ * their size); all zero after a reset (lpcnet_encoder_init). */
+constexpr int NTF = 36;          /* NB_TOTAL_FEATURES */
+constexpr int PITCH_MIN = 32;    /* PITCH_MIN_PERIOD (lpcnet_private.h:14) */
+constexpr int PITCH_MAX = 256;   /* PITCH_MAX_PERIOD */
+constexpr int PITCH_STATES = PITCH_MAX - PITCH_MIN; /* Viterbi states */
+struct alignas(16) FeatState {
+  float analysis_mem[FRAME];        /* the previous frame's preemphasised input */
+  float exc[PITCH_MAX];             /* exc_buf[FRAME .. FRAME + PITCH_MAX) after the previous frame */
+  float pitch_max_path[PITCH_MAX];  /* pitch_max_path[0] */
+  float pitch_mem[NLPC];
+  float mem_preemph, pitch_filt, pitch_max_path_all;
+  int best_i;                       /* in [0, PITCH_STATES) */
+};
+/* host-built constants: half_window (dump_lpcnet_tables.c:83-84) and, per
+ * spectrum bin below 160, (float)j/band_size (freq.c:141) */
+struct FeatTables {
+  float half_window[FRAME];
+  float frac[FRAME];
+  int band_start[NBANDS]; /* eband5ms[b] * WINDOW_SIZE_5MS (freq.c:45-48, 138) */
+  int pad[2];
+};
+struct FeatArgs {
+  int nstreams;
+  const short *pcm;            /* [B][FRAME], or */
+  const float *pcm_f;          /* [B][FRAME] when pcm is null */
+  float *features;             /* [B][row] */
+  int row;                     /* NF or NTF */
+  const unsigned char *active; /* [B]; null: every stream */
+  FeatState *state;            /* [B] */
+  const LpcTables *lpc_tab;
+  const FeatTables *tab;
+};
+int launch_feat(const FeatArgs &a, void *stream);
+
 }  // namespace lpcnet_mi355x
 
 #endif

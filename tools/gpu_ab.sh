@@ -27,7 +27,7 @@ line() {  # bench.py JSON line -> one summary line
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]
-print("%-28s value %8.4gM step %.4f ms kernel/frame %.4f ms" % (sys.argv[2], d["value"] / 1e6, d["ms_per_step"], r["ms_per_frame"]))
+print("%-28s value %8.4gM step %.4f ms kernel/frame %.4f ms" % (sys.argv[2], d["value"] / 1e6, d["ms_per_step"], r.get("ms_per_frame", d.get("frame_step_ms", float("nan")))))
 PY
 }
 if [ -n "$K" ]; then
