@@ -396,6 +396,14 @@ __device__ __forceinline__ void ga_arrived(float (&v)[4][3])
  *
  *   r front | z front | r back | h front | z back, zv*st, 1-zv | h back, update
  *
+ * HLATE: only the r and z rows are in flight on entry, and the h rows' loads
+ * (issue_h) go out behind the r front.  A wave cannot run ahead of a load it
+ * has not issued yet, and the CU takes the six waves' 216 loads at about one
+ * per 4 cycles: issuing all 36 first kept the youngest waves from their r
+ * front until about 1,100 cycles after barrier X, with their r rows long
+ * there.  The r wait's count drops from 6S to
+ * 3S; the z wait's stays 3S (the h rows are behind the z rows as before).
+ *
  * In the select-free branch the r reads are consumed 74 instructions after
  * their issue and the h reads 40.  The z reads are awaited after 18 already:
  * the h conditioning is read from LDS behind them (LDS returns in order), and
@@ -414,12 +422,13 @@ __device__ __forceinline__ void ga_arrived(float (&v)[4][3])
  * and r back, 12 = h front and z back, 13 = h back and the state update.
  * (The parent order with stamps around each stage's table reads, the build
  * behind profiles/r09/exposure_parent.txt: profiles/r09/exposure_build.patch.) */
-template <int S, bool FAST, bool HW, int TB = RCP_TABLE_BITS, typename Stamp>
+template <int S, bool FAST, bool HW, bool HLATE, int TB = RCP_TABLE_BITS, typename Stamp, typename IssueH>
 __device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)[3][S][3], const float *cnd, int tid,
                                                       const float (&faz)[S], const float (&far)[S],
                                                       const float (&tz)[S], const float (&tr)[S],
                                                       const float (&hpre)[S], const uint32_t *rcp,
-                                                      unsigned char *xa_i, bool stamping, Stamp &stamp)
+                                                      unsigned char *xa_i, bool stamping, Stamp &stamp,
+                                                      IssueH &issue_h)
 {
   static_assert(S == 4, "staged form: four streams per lane (ga_arrived)");
   static_assert(!HW, "staged form: the table reciprocal (four streams per lane are VALU-bound)");
@@ -455,12 +464,17 @@ __device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)
       tanh_x86_back_n(hv, hn, hd, ht);
   };
   /* r front */
-  ga_arrived<6 * S>(e[0]);
+  ga_arrived<(HLATE ? 3 : 6) * S>(e[0]);
   if (stamping) stamp(10);
   for (int s = 0; s < S; s++) rv[s] = pre(e[0][s], c[1][s], far[s], tr[s]);
   sigmoid_x86_poly_n(rv, rn, rd);
   rcp_issue_n<S, TB>(rd, rt, rcp);
   __builtin_amdgcn_sched_barrier(0);
+  if constexpr (HLATE) {
+    /* the h rows' loads, under the r reads: the z rows stay 3S loads back */
+    issue_h();
+    __builtin_amdgcn_sched_barrier(0);
+  }
   /* z front, under the r reads */
   ga_arrived<3 * S>(e[1]);
   for (int s = 0; s < S; s++) zv[s] = pre(e[1][s], c[0][s], faz[s], tz[s]);

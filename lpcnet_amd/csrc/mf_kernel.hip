@@ -21,7 +21,12 @@
  * Per sample n, two workgroup barriers:
  *   X  ix(n) published: GRU_A waves gather the embedding rows and run the
  *      GRU_A elementwise step -> q(h_A(n)); samplers: deferred bookkeeping of
- *      n-1, kiss99 draws
+ *      n-1, kiss99 draws.  Four streams per lane, unsplit: a wave issues its r and z
+ *      rows (waves 4/5, the younger waves of SIMDs 0/1, their r rows at
+ *      raised priority) and its h rows only behind the r stage's front half:
+ *      the CU takes the 216 loads at one per ~4 cycles and a wave stands at
+ *      a load until it is taken, so a wave that issues everything first
+ *      starts its r stage with the whole burst, not with its r rows
  *   Y  q(h_A(n)) complete: GRU_A waves: W q(h_A(n)) for sample n+1;
  *      samplers: GRU_B products + update, dual-FC tree walk -> ix(n+1)
  * The arithmetic is term for term the reference's (see device_math.h).
@@ -98,6 +103,17 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
    * box, 513 / 768 streams: +0.2 / -0.5 %) and keep the stream-major form */
   constexpr bool kStaged = S == 4;
   constexpr bool kGbwLds = S == 4;
+  /* the unsplit staged form issues its h rows behind the r stage's front
+   * half (ga_elementwise_staged).  The split instances keep all 36 loads up
+   * front: with the h rows' offsets live through the r front they spill five
+   * registers that the recurrent product reloads every sample (skewed model
+   * at 1024 streams: -15 %).  So does the arrival build (-DMF_ARRIVAL: no
+   * work between the gathers and their arrival). */
+#ifdef MF_ARRIVAL
+  constexpr bool kHLate = false;
+#else
+  constexpr bool kHLate = kStaged && !SPLIT;
+#endif
 
   bool active[S];
   bool any = false;
@@ -368,34 +384,61 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
           /* GRU_A input (nnet.c:484-491): all 9*S gathers in flight at once */
           [[maybe_unused]] float e[S][9];     /* [stream][table * 3 + gate] */
           [[maybe_unused]] float eg[3][S][3]; /* kStaged: [gate in issue order r, z, h][stream][table] */
+          [[maybe_unused]] uint32_t o[S][3];  /* kStaged: row + lane offset [stream][table] */
+          /* kStaged: the loads of the k-th gate issued (r, z, h), all streams
+           * and tables; table base in SGPRs, row + lane offset in one 32-bit
+           * VGPR (the global_load saddr form, see below) */
+          [[maybe_unused]] auto issue_gate = [&](int k) __attribute__((always_inline)) {
+            const char *b1 = (const char *)A.mf_emb[0], *b2 = (const char *)A.mf_emb[1], *b3 = (const char *)A.mf_emb[2];
+            const uint32_t g = k < 2 ? 1 - k : k; /* table gate */
+            for (int s = 0; s < S; s++) asm volatile("" : "+v"(o[s][0]), "+v"(o[s][1]), "+v"(o[s][2]));
+            for (int s = 0; s < S; s++) {
+              eg[k][s][0] = *(const float *)(b1 + o[s][0] + g * NA * 4u);
+              eg[k][s][1] = *(const float *)(b2 + o[s][1] + g * NA * 4u);
+              eg[k][s][2] = *(const float *)(b3 + o[s][2] + g * NA * 4u);
+            }
+            __builtin_amdgcn_sched_barrier(0); /* the gates' loads stay in this order */
+#ifdef MF_ARRIVAL
+            stamp(11 + k);
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+          };
+          [[maybe_unused]] auto issue_h = [&]() __attribute__((always_inline)) { issue_gate(2); };
           if constexpr (kStaged) {
-            /* gate-major: the r rows of every stream, then the z rows, then
-             * the h rows.  The loads return in issue order, so the staged
-             * elementwise step starts on the first third of the bytes while
-             * the rest is in flight (z is not needed before the state
-             * update: r first).  Every stream's indices are read before the
-             * first gather; table base in SGPRs, row + lane offset in one
-             * 32-bit VGPR (the global_load saddr form, see below). */
+            /* gate-major: the r rows of every stream, then the z rows; the h
+             * rows from inside the staged elementwise step, behind the r
+             * front (kHLate).  The loads return in issue order, and a wave
+             * stands at a load until the CU takes it (all six waves' 216
+             * loads at about one per 4 cycles), so the r stage starts once
+             * two thirds are issued, and on the first third of the bytes (z
+             * is not needed before the state update: r first).  Every
+             * stream's indices are read before the first gather. */
             int4 ixv[S];
             for (int s = 0; s < S; s++) ixv[s] = *(const int4 *)(ix + s * 4);
-            uint32_t o[S][3];
             for (int s = 0; s < S; s++) {
               o[s][0] = (uint32_t)tid * 4u + (uint32_t)ixv[s].x;
               o[s][1] = (uint32_t)tid * 4u + (uint32_t)ixv[s].y;
               o[s][2] = (uint32_t)tid * 4u + (uint32_t)ixv[s].z;
             }
-            const char *b1 = (const char *)A.mf_emb[0], *b2 = (const char *)A.mf_emb[1], *b3 = (const char *)A.mf_emb[2];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-              const uint32_t g = k < 2 ? 1 - k : k; /* table gate of the k-th issued: r, z, h */
-              for (int s = 0; s < S; s++) asm volatile("" : "+v"(o[s][0]), "+v"(o[s][1]), "+v"(o[s][2]));
-              for (int s = 0; s < S; s++) {
-                eg[k][s][0] = *(const float *)(b1 + o[s][0] + g * NA * 4u);
-                eg[k][s][1] = *(const float *)(b2 + o[s][1] + g * NA * 4u);
-                eg[k][s][2] = *(const float *)(b3 + o[s][2] + g * NA * 4u);
-              }
-              __builtin_amdgcn_sched_barrier(0); /* the gates' loads stay in this order */
-            }
+#ifdef MF_ARRIVAL
+            /* diagnostic build: the issue of this wave's first load (stamp 3)
+             * and of each gate's last (11, 12, 13) */
+            for (int s = 0; s < S; s++) asm volatile("" : "+v"(o[s][0]), "+v"(o[s][1]), "+v"(o[s][2]));
+            __builtin_amdgcn_sched_barrier(0);
+            stamp(3);
+#endif
+            /* waves 4/5 share SIMDs 0/1 with the older waves 0/1, which win
+             * the issue at equal priority and put their r and z rows ahead
+             * of these waves' r rows: the r rows of both first */
+#ifndef MF_PRIO45
+            if (kHLate && wv >= 4) __builtin_amdgcn_s_setprio(1);
+#endif
+            issue_gate(0);
+#ifndef MF_PRIO45
+            if (kHLate && wv >= 4) __builtin_amdgcn_s_setprio(0);
+#endif
+            issue_gate(1);
+            if constexpr (!kHLate) issue_gate(2);
           } else if constexpr (S > 1) {
             /* split form: every stream's indices read before the first
              * gather (one LDS wait instead of one per stream: skewed model at
@@ -487,7 +530,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
           }
 #ifdef MF_ARRIVAL
           /* diagnostic build: when each third of the gate-major gathers has
-           * arrived, no work in between (stamps 8, 9, 10) */
+           * arrived, no work in between (stamps 8, 9, 10), behind the issue
+           * stamps above (3, 11, 12, 13) */
           if constexpr (stamping && kStaged) {
             __builtin_amdgcn_sched_barrier(0);
             ga_arrived<6 * S>(eg[0]);
@@ -501,9 +545,9 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
            * branch per sample into straight-line code for all S streams */
           if constexpr (kStaged) {
             if (__builtin_amdgcn_readfirstlane((int)fast))
-              ga_elementwise_staged<S, true, kHwA>(st, eg, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
+              ga_elementwise_staged<S, true, kHwA, kHLate>(st, eg, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp, issue_h);
             else
-              ga_elementwise_staged<S, false, kHwA>(st, eg, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
+              ga_elementwise_staged<S, false, kHwA, kHLate>(st, eg, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp, issue_h);
           } else if (__builtin_amdgcn_readfirstlane((int)fast))
             ga_elementwise<S, true, kHwA>(st, e, cnd, tid, faz, far, tz, tr, hpre, rcp, xa + i, stamping, stamp);
           else
