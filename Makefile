@@ -2,6 +2,7 @@
 #
 #   make            -> lpcnet_amd/liblpcnet_mi355x.so + oracle/ libraries
 #   make lib        -> the product library only
+#   make check      -> builds and runs tools/model_host_check (CPU only)
 #
 # Every translation unit is compiled with -ffp-contract=off: the engine is
 # bit-exact with the reference x86 build only without FMA contraction.
@@ -12,15 +13,15 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
 
-all: lib synth dropin oracle
+all: lib synth dropin hostcheck oracle
 
 lib: $(LIB)
 
@@ -85,6 +86,13 @@ $(BUILD)/feat_kernel.o: $(CSRC)/feat_kernel.hip $(HDRS) | $(BUILD)
 $(BUILD)/model_gen.o: $(CSRC)/model_gen.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
+# host-only code: the GRU_A planner and the blob -> HostModel ingest
+$(BUILD)/mf_plan.o: $(CSRC)/mf_plan.cpp $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
+$(BUILD)/model_host.o: $(CSRC)/model_host.cpp $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
 # host-only: the CPU's own rcpps (x86 SSE), system compiler
 $(BUILD)/host_rcpps.o: $(CSRC)/host_rcpps.cpp include/lpcnet_mi355x.h | $(BUILD)
 	$(CXX) -O2 -fPIC -msse2 -ffp-contract=off -std=c++17 -Iinclude -fvisibility=hidden -Wall -c $< -o $@
@@ -92,11 +100,26 @@ $(BUILD)/host_rcpps.o: $(CSRC)/host_rcpps.cpp include/lpcnet_mi355x.h | $(BUILD)
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lpthread
 
+# stand-alone CPU check of the model tables over the host-only objects
+# (tools/model_host_check.cpp gives the sanitizer recipe)
+HOSTCHECK := tools/model_host_check
+
+$(BUILD)/model_host_check.o: tools/model_host_check.cpp $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
+$(HOSTCHECK): $(BUILD)/model_host_check.o $(BUILD)/model_host.o $(BUILD)/mf_plan.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o
+	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
+
+hostcheck: $(HOSTCHECK)
+
+check: $(HOSTCHECK)
+	$(HOSTCHECK)
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN)
+	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib synth dropin oracle clean
+.PHONY: all lib synth dropin hostcheck oracle clean check

@@ -291,6 +291,33 @@ LPCNET_EXPORT int lpcnet_mi355x_device_numerics(int device, int op, const void *
  * (parse_lpcnet_weights.c:36-113 record/idx rules, array sizes, LDS budget)
  * without a device.  Returns 0 or -1 (lpcnet_mi355x_last_error). */
 LPCNET_EXPORT int lpcnet_mi355x_validate_model(const unsigned char *data, int len);
+/* Host-only digests of everything a load of the blob would hand a batch of
+ * `streams` streams: one FNV-1a-64 per entry, in this order:
+ *   [0]      the sample kernels' argument block (scalars; its device
+ *            pointers null);
+ *   [1..56]  the device tables, as uploaded: the frame network's conv1_w,
+ *            conv1_b, conv2_w, conv2_b, dense1_w, dense1_b, dense2_w,
+ *            dense2_b, gadf_w, gadf_b, gbdf_w, gbdf_b, proj_w, proj_b,
+ *            ck_conv1, ck_conv2, ck_dense1, ck_dense2, ck_proj, embed_pitch,
+ *            rcp; the sample kernels' emb_sig, emb_pred, emb_exc, ga_par,
+ *            ga_wsum, gb_par, gb_wsum, image, mf, mf_unit, mf_frow, mfw_tab,
+ *            mfw_frow, mfw_unit, mf_emb[0..2], mfw_emb[0..2], mf_gb, fp_zr,
+ *            fp_h, fp_off, fpl_zr, fpl_h, fpl_off, fp_gb, ga_wf, gb_recf; the
+ *            decoder's cb1, cb2, cb3, cbd, pitch (0: the model has no such
+ *            table);
+ *   [57]     the chunk kernel's four replication strides;
+ *   [58]     variant, may-saturate, quad layout, matrix-core / fp32-kernel
+ *            tables present, codebooks, wide plan, custom rcpps, the lockstep
+ *            kernel's streams per workgroup and LDS bytes, GRU_A and GRU_B
+ *            block counts (ints);
+ *   [59]     bytes_shared_per_frame, bytes_shared_per_sample,
+ *            bytes_per_stream_sample, ops_per_sample, the matrix-core GRU_A
+ *            and GRU_B ops per group and sample (doubles).
+ * wide: 1 / 0 = the register tables are planned for mfw_kernel or not; -1 =
+ * as a batch on a device of `cus` compute units decides.  Returns the number
+ * of entries written (60; cap must hold them) or -1. */
+LPCNET_EXPORT int lpcnet_mi355x_model_digest(const unsigned char *data, int len, int streams, int cus, int wide, uint64_t *out,
+                                             int cap);
 /* Number of visible HIP devices (0 on a machine without GPU). */
 LPCNET_EXPORT int lpcnet_mi355x_device_count(void);
 /* Host-only view of the GRU_A plans a blob (data, len) gets on a wide batch

@@ -51,7 +51,7 @@ constexpr int MF_ZMAX = 16;         /* z / r slots per lane */
 constexpr int MF_HMAX = 32;         /* h slots per lane */
 constexpr int MF_GA = 2 * MF_ZMAX + MF_HMAX;
 constexpr int MF_LANE_U32 = MF_GA + MF_GA / 4; /* 80 */
-/* mfw_kernel split form (engine.cpp mfw_split_tables): two host waves after
+/* mfw_kernel split form (mf_plan.cpp mfw_split_tables): two host waves after
  * the six R waves carry the pieces of block rows beyond the register caps */
 constexpr int MFW_H_WAVES = 2;
 constexpr int MFW_TAB_WAVES = 6 + MFW_H_WAVES; /* SAMPLE_WAVES R waves + the host waves */
@@ -245,7 +245,7 @@ struct SampleArgs {
                                         [256][3][SAMPLE_WAVES * 64], column p = unit mf_unit[p] */
   int mf_nzr[SAMPLE_WAVES];          /* own 4-slot groups per GRU_A wave: z and r */
   int mf_nh[SAMPLE_WAVES];           /* h */
-  /* split models (rows longer than the own cap, engine.cpp mf_plan): hosted
+  /* split models (rows longer than the own cap, mf_plan.cpp mf_plan): hosted
    * 4-slot groups after the own ones, the row each lane's hosted partial
    * sums belong to [3 gates][SAMPLE_WAVES * 64] (NA: none) */
   int mf_split;

@@ -1,0 +1,282 @@
+/*
+ * model_host_check.cpp -- the matrix-core tables of a model load, decoded
+ * back into the matrices they stand for, on the CPU.  A stand-alone program
+ * over the host-only objects of the library (no device, no Python):
+ *
+ *   make check        (builds and runs tools/model_host_check)
+ *
+ * For the int8 synthetic models (default, skewed: split plans) in every plan
+ * class (1, 512, 1024, 2048 streams; 8192 streams planned for the wide
+ * kernel), and again with every plan forced to split, it decodes
+ *   - mf / mf_unit / mf_frow (own and hosted regions, through the slots'
+ *     column bytes) and
+ *   - mfw_tab / mfw_unit / mfw_frow (R waves, host waves, part rows)
+ * into a dense 1152 x 384 GRU_A recurrent matrix that must equal the one
+ * assembled from the blob's index and weights: every block exactly once, at
+ * its column, in a row whose partial sum reaches the right unit.  It also
+ * checks the slot budgets of every wave (4 (nzr + nfzr) <= MF_ZMAX,
+ * 4 (nh + nfh) <= MF_HMAX), that a lane group hosts at most one piece per
+ * gate, and that the dense GRU_B tiles decode to the blob's GRU_B.
+ *
+ * Under AddressSanitizer and UBSan (host code only):
+ *
+ *   make build_san/mf_plan.o build_san/model_host.o build_san/model_gen.o build_san/host_rcpps.o BUILD=build_san \
+ *        EXTRA="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer"
+ *   /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Iinclude -Ilpcnet_amd/csrc \
+ *        -Xarch_host -fsanitize=address,undefined -c tools/model_host_check.cpp -o build_san/model_host_check.o
+ *   /opt/rocm/llvm/bin/clang++ -fsanitize=address,undefined -o build_san/model_host_check build_san/model_host_check.o \
+ *        build_san/model_host.o build_san/mf_plan.o build_san/model_gen.o build_san/host_rcpps.o
+ *   (the compiler hipcc drives: the objects' sanitizer calls need its runtime)
+ *   build_san/model_host_check
+ *
+ * Exit status 0 and one "model_host_check ok" line when every check holds.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <set>
+#include <vector>
+
+#include "model_host.h"
+
+using namespace lpcnet_mi355x;
+
+static int fails;
+
+#define CHECK(cond, ...)                                    \
+  do {                                                      \
+    if (!(cond)) {                                          \
+      if (fails++ < 20) {                                   \
+        fprintf(stderr, "line %d: %s: ", __LINE__, #cond);  \
+        fprintf(stderr, __VA_ARGS__);                       \
+        fprintf(stderr, "\n");                              \
+      }                                                     \
+    }                                                       \
+  } while (0)
+
+typedef std::vector<int> Mat; /* [rows][NA] */
+
+static int gate_base(int g) { return g == 0 ? 0 : (g == 1 ? MF_ZMAX : 2 * MF_ZMAX); }
+
+/* slots [s0, s0 + n) of lane l of a wave's table [MF_LANE_U32][64] added into row `row` of D
+ * (row < 0: the slots must hold zero weights) */
+static void add_slots(const uint32_t *wtab, int l, int s0, int n, int row, Mat &D, const char *what)
+{
+  for (int s = s0; s < s0 + n; s++) {
+    int8_t w[4];
+    memcpy(w, &wtab[(size_t)s * 64 + l], 4);
+    const int cb = (wtab[(size_t)(MF_GA + s / 4) * 64 + l] >> (8 * (s & 3))) & 0xFF;
+    CHECK(cb < NA / 4, "%s: lane %d slot %d column block %d", what, l, s, cb);
+    if (cb >= NA / 4) continue;
+    for (int c = 0; c < 4; c++) {
+      if (row < 0) CHECK(w[c] == 0, "%s: lane %d slot %d has weights but no row", what, l, s);
+      else D[(size_t)row * NA + 4 * cb + c] += w[c];
+    }
+  }
+}
+
+/* slots of a lane's table outside [s0, s0 + n) of gate g's range must be zero */
+static void check_unused(const uint32_t *wtab, int l, int g, int used, const char *what)
+{
+  const int end = gate_base(g) + (g < 2 ? MF_ZMAX : MF_HMAX);
+  for (int s = gate_base(g) + used; s < end; s++)
+    CHECK(wtab[(size_t)s * 64 + l] == 0, "%s: lane %d unused slot %d holds weights", what, l, s);
+}
+
+static void compare(const Mat &D, const Mat &R, const char *what, const char *tag)
+{
+  size_t bad = 0, first = 0;
+  for (size_t i = 0; i < R.size(); i++)
+    if (D[i] != R[i] && !bad++) first = i;
+  CHECK(bad == 0, "%s %s: %zu entries differ, first at row %zu column %zu (%d, blob %d)", tag, what, bad, first / NA,
+        first % NA, D[first], R[first]);
+}
+
+static void check_mf(const HostModel &H, const Mat &R, const char *tag)
+{
+  const SampleArgs &sa = H.sa;
+  Mat D(R.size(), 0);
+  CHECK(H.mf.tab.size() == (size_t)SAMPLE_WAVES * MF_LANE_U32 * 64 && H.mf.units.size() == (size_t)SAMPLE_WAVES * 64 &&
+            H.mf.frow.size() == (size_t)3 * SAMPLE_WAVES * 64,
+        "%s: table sizes", tag);
+  std::set<int> units(H.mf.units.begin(), H.mf.units.end());
+  CHECK((int)units.size() == NA && *units.begin() == 0 && *units.rbegin() == NA - 1, "%s: mf_unit is not a permutation", tag);
+  std::set<int> merged[3], hosted[3]; /* unit blocks whose lanes merge pieces / that pieces go to */
+  for (int w = 0; w < SAMPLE_WAVES; w++) {
+    CHECK(4 * (sa.mf_nzr[w] + sa.mf_nfzr[w]) <= MF_ZMAX, "%s: wave %d z/r groups %d + %d", tag, w, sa.mf_nzr[w], sa.mf_nfzr[w]);
+    CHECK(4 * (sa.mf_nh[w] + sa.mf_nfh[w]) <= MF_HMAX, "%s: wave %d h groups %d + %d", tag, w, sa.mf_nh[w], sa.mf_nfh[w]);
+    CHECK(sa.mf_split || (sa.mf_nfzr[w] == 0 && sa.mf_nfh[w] == 0), "%s: hosted groups in an unsplit plan", tag);
+    const uint32_t *wtab = &H.mf.tab[(size_t)w * MF_LANE_U32 * 64];
+    for (int l = 0; l < 64; l++) {
+      const int unit = H.mf.units[w * 64 + l];
+      CHECK(unit % 8 == l % 8 && unit / 8 == H.mf.units[w * 64 + (l & ~7)] / 8, "%s: lane %d of wave %d unit %d", tag, l, w, unit);
+      for (int g = 0; g < 3; g++) {
+        const int nown = 4 * (g < 2 ? sa.mf_nzr[w] : sa.mf_nh[w]), nfor = 4 * (g < 2 ? sa.mf_nfzr[w] : sa.mf_nfh[w]);
+        const int fr = H.mf.frow[((size_t)g * SAMPLE_WAVES + w) * 64 + l], target = fr & 0xFFFF;
+        if (fr >> 16) merged[g].insert(unit / 8);
+        add_slots(wtab, l, gate_base(g), nown, g * NA + unit, D, tag);
+        /* one piece per lane group and gate: its 8 lanes carry rows 8 u .. 8 u + 7 of one unit block u, or none */
+        const int t0 = H.mf.frow[((size_t)g * SAMPLE_WAVES + w) * 64 + (l & ~7)] & 0xFFFF;
+        CHECK(target == NA ? t0 == NA : (target < NA && target == t0 + l % 8 && t0 % 8 == 0), "%s: wave %d lane %d gate %d hosted row %d",
+              tag, w, l, g, target);
+        if (target < NA) hosted[g].insert(target / 8);
+        add_slots(wtab, l, gate_base(g) + nown, nfor, target < NA ? g * NA + target : -1, D, tag);
+        check_unused(wtab, l, g, nown + nfor, tag);
+      }
+    }
+  }
+  for (int g = 0; g < 3; g++) CHECK(merged[g] == hosted[g], "%s: gate %d merge flags do not match the hosted pieces", tag, g);
+  compare(D, R, "mf tables", tag);
+}
+
+static void check_mfw(const HostModel &H, const Mat &R, const char *tag)
+{
+  constexpr int FS = SAMPLE_THREADS + 64 * MFW_H_WAVES;
+  const SampleArgs &sa = H.sa;
+  const MfwSplitTab &T = H.mfw;
+  Mat D(R.size(), 0);
+  CHECK(T.tab.size() == (size_t)MFW_TAB_WAVES * MF_LANE_U32 * 64 && T.units.size() == (size_t)SAMPLE_THREADS &&
+            T.frow.size() == (size_t)3 * FS,
+        "%s: wide table sizes", tag);
+  std::set<int> units(T.units.begin(), T.units.end());
+  CHECK((int)units.size() == NA, "%s: mfw_unit is not a permutation", tag);
+  for (int g = 0; g < 3; g++) {
+    /* part row -> unit, from the E threads' merge entries */
+    std::vector<int> unit_of(MFW_PART_ROWS, -1);
+    for (int t = 0; t < SAMPLE_THREADS; t++) {
+      const int fr = T.frow[(size_t)g * FS + t];
+      if (fr == MFW_NOROW) continue;
+      const int pr = fr & 0xFFFF;
+      CHECK(fr >> 16 == 1 && pr < MFW_PART_ROWS && pr % 8 == t % 8, "%s: gate %d thread %d entry %#x", tag, g, t, fr);
+      if (pr >= MFW_PART_ROWS) continue;
+      CHECK(unit_of[pr] < 0, "%s: gate %d part row %d merged twice", tag, g, pr);
+      unit_of[pr] = T.units[t];
+    }
+    for (int w = 0; w < MFW_TAB_WAVES; w++) {
+      const int n = 4 * (g < 2 ? sa.mfw_nzr[w] : sa.mfw_nh[w]);
+      CHECK(n >= 4 && n <= (g < 2 ? MF_ZMAX : MF_HMAX), "%s: table wave %d gate %d slots %d", tag, w, g, n);
+      CHECK(sa.mfw_nzr[w] == T.nzr[w] && sa.mfw_nh[w] == T.nh[w], "%s: table wave %d group counts", tag, w);
+      const uint32_t *wtab = &T.tab[(size_t)w * MF_LANE_U32 * 64];
+      for (int l = 0; l < 64; l++) {
+        int row = -1;
+        if (w < SAMPLE_WAVES) {
+          row = g * NA + T.units[w * 64 + l];
+        } else {
+          const int pr = T.frow[(size_t)g * FS + SAMPLE_THREADS + (w - SAMPLE_WAVES) * 64 + l];
+          const int p0 = T.frow[(size_t)g * FS + SAMPLE_THREADS + (w - SAMPLE_WAVES) * 64 + (l & ~7)];
+          CHECK(pr == MFW_NOROW ? p0 == MFW_NOROW : (pr < MFW_PART_ROWS && p0 % 8 == 0 && pr == p0 + l % 8),
+                "%s: host wave %d lane %d gate %d part row %d", tag, w, l, g, pr);
+          if (pr != MFW_NOROW && pr < MFW_PART_ROWS) {
+            CHECK(unit_of[pr] >= 0, "%s: gate %d part row %d has no owner", tag, g, pr);
+            if (unit_of[pr] >= 0) row = g * NA + unit_of[pr];
+          }
+        }
+        add_slots(wtab, l, gate_base(g), n, row, D, tag);
+        check_unused(wtab, l, g, n, tag);
+      }
+    }
+  }
+  compare(D, R, "wide split tables", tag);
+}
+
+/* the dense GRU_B tiles against the blob's GRU_B (input: block-sparse; recurrent: [rb][cb][8][4]) */
+static void check_gru_b(const HostModel &H, const char *tag)
+{
+  std::vector<std::vector<int>> gb;
+  const Arr *w = find(H.records, "gru_b_weights"), *r = find(H.records, "gru_b_recurrent_weights");
+  if (!parse_idx(H.records, "gru_b_weights_idx", NA, GB_ROWS, gb) || !w || !r) {
+    CHECK(false, "%s: GRU_B records", tag);
+    return;
+  }
+  std::vector<int> Rin((size_t)GB_ROWS * NA, 0), Rrec((size_t)GB_ROWS * NB, 0), Din(Rin.size(), 0), Drec(Rrec.size(), 0);
+  const int8_t *wb = (const int8_t *)w->data, *wr = (const int8_t *)r->data;
+  int k = 0;
+  for (int rb = 0; rb < GB_ROWS / 8; rb++)
+    for (int pos : gb[rb]) {
+      for (int i = 0; i < 8; i++)
+        for (int c = 0; c < 4; c++) Rin[(size_t)(rb * 8 + i) * NA + pos + c] += wb[32 * k + 4 * i + c];
+      k++;
+    }
+  for (int rb = 0; rb < GB_ROWS / 8; rb++)
+    for (int cb = 0; cb < NB / 4; cb++)
+      for (int i = 0; i < 8; i++)
+        for (int c = 0; c < 4; c++) Rrec[(rb * 8 + i) * NB + 4 * cb + c] = wr[32 * (rb * (NB / 4) + cb) + 4 * i + c];
+  CHECK(H.mf_gb.size() == (size_t)MF_GB_TILES * 64 * 4, "%s: GRU_B tile size", tag);
+  if (H.mf_gb.size() != (size_t)MF_GB_TILES * 64 * 4) return;
+  const int8_t *tiles = (const int8_t *)H.mf_gb.data();
+  for (int g = 0; g < 3; g++)
+    for (int l = 0; l < 64; l++) {
+      const int row = 16 * g + (l & 15), k0 = 16 * (l >> 4);
+      for (int kt = 0; kt < 6; kt++)
+        for (int j = 0; j < 16; j++) Din[(size_t)row * NA + 64 * kt + k0 + j] += tiles[((size_t)(g * 6 + kt) * 64 + l) * 16 + j];
+      for (int j = 0; j < 16; j++) {
+        const int v = tiles[((size_t)(MF_GB_IN + g) * 64 + l) * 16 + j];
+        if (k0 == 0) Drec[row * NB + j] += v;
+        else CHECK(v == 0, "%s: recurrent tile %d lane %d byte %d", tag, g, l, j);
+      }
+    }
+  CHECK(Din == Rin, "%s: GRU_B input tiles differ from the blob", tag);
+  CHECK(Drec == Rrec, "%s: GRU_B recurrent tiles differ from the blob", tag);
+}
+
+int main(void)
+{
+  static const struct { const char *name; int flags; bool mf; } models[] = {
+      {"int8", 0, true}, {"int8_saturating", 1, false}, {"int8_skewed", 2, true}};
+  static const struct { int streams; bool wide; } classes[] = {{1, false}, {512, false}, {1024, false}, {2048, false}, {8192, true}};
+  static const char *const hooks[] = {"LPCNET_MF_ITERS", "LPCNET_MF_SIMD_W", "LPCNET_MF_HOSTED_F", "LPCNET_MF_PIECE_W",
+                                      "LPCNET_MF_CAPS", "LPCNET_MF_FORCE_SPLIT", "LPCNET_NO_MFMA", "LPCNET_NO_MFW_SPLIT",
+                                      "LPCNET_RCP", "LPCNET_VERBOSE"};
+  for (const char *h : hooks) unsetenv(h);
+  int plans = 0, split = 0, wide = 0;
+  for (int force = 0; force < 2; force++) {
+    if (force) setenv("LPCNET_MF_FORCE_SPLIT", "1", 1);
+    for (const auto &m : models) {
+      const int n = lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, m.flags, nullptr, 0);
+      std::vector<unsigned char> blob(n);
+      lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, m.flags, blob.data(), n);
+      /* the matrix the tables must decode to */
+      std::vector<Arr> L;
+      GruASparse A;
+      if (!parse_blob(L, blob.data(), n) || parse_gru_a(L, A) || A.variant != LPCNET_VARIANT_INT8) {
+        CHECK(false, "%s: synthetic blob does not parse (%s)", m.name, last_err().c_str());
+        continue;
+      }
+      Mat R((size_t)GA_ROWS * NA, 0);
+      for (int rb = 0; rb < GA_ROWS / 8; rb++)
+        for (int t = 0; t < (int)A.blocks[rb].size(); t++)
+          for (int r = 0; r < 8; r++)
+            for (int c = 0; c < 4; c++)
+              R[(size_t)(rb * 8 + r) * NA + A.blocks[rb][t] + c] += ((const int8_t *)A.w)[32 * (A.first[rb] + t) + 4 * r + c];
+      for (const auto &c : classes) {
+        char tag[96];
+        snprintf(tag, sizeof tag, "%s/%d%s%s", m.name, c.streams, c.wide ? "/wide" : "", force ? "/forced split" : "");
+        ModelBuildOpts opts;
+        opts.streams = c.streams;
+        opts.wide = c.wide;
+        HostModel H;
+        if (build_host_model(blob.data(), n, opts, H)) {
+          CHECK(false, "%s: build failed: %s", tag, last_err().c_str());
+          continue;
+        }
+        CHECK(H.mf_ok == m.mf, "%s: matrix-core tables %d", tag, H.mf_ok);
+        if (!H.mf_ok) continue;
+        CHECK(!force || H.sa.mf_split, "%s: plan not split", tag);
+        CHECK(H.sa.mfw_split == (H.sa.mf_split && c.wide ? 1 : 0), "%s: wide split form %d", tag, H.sa.mfw_split);
+        check_mf(H, R, tag);
+        if (H.sa.mfw_split) check_mfw(H, R, tag);
+        check_gru_b(H, tag);
+        plans++;
+        split += H.sa.mf_split;
+        wide += H.sa.mfw_split;
+      }
+    }
+  }
+  if (fails) {
+    fprintf(stderr, "model_host_check: %d checks failed\n", fails);
+    return 1;
+  }
+  printf("model_host_check ok (%d plans decoded, %d split, %d with the wide split form)\n", plans, split, wide);
+  return 0;
+}
