@@ -2,7 +2,8 @@
 #
 #   make            -> lpcnet_amd/liblpcnet_mi355x.so + oracle/ libraries
 #   make lib        -> the product library only
-#   make check      -> builds and runs tools/model_host_check (CPU only)
+#   make check      -> builds and runs tools/model_host_check and
+#                      tools/pool_combiner_check (CPU only)
 #
 # Every translation unit is compiled with -ffp-contract=off: the engine is
 # bit-exact with the reference x86 build only without FMA contraction.
@@ -13,10 +14,10 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
@@ -67,6 +68,10 @@ $(BUILD)/selftest.o: $(CSRC)/selftest.hip $(HDRS) | $(BUILD)
 $(BUILD)/engine.o: $(CSRC)/engine.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
+# the drop-in single-stream API over the batch engine (batch.h)
+$(BUILD)/dropin.o: $(CSRC)/dropin.cpp $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
 $(BUILD)/lpc_kernel.o: $(CSRC)/lpc_kernel.hip $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
@@ -97,6 +102,11 @@ $(BUILD)/model_host.o: $(CSRC)/model_host.cpp $(HDRS) | $(BUILD)
 $(BUILD)/host_rcpps.o: $(CSRC)/host_rcpps.cpp include/lpcnet_mi355x.h | $(BUILD)
 	$(CXX) -O2 -fPIC -msse2 -ffp-contract=off -std=c++17 -Iinclude -fvisibility=hidden -Wall -c $< -o $@
 
+# host-only: the drop-in pools' flat combiner (futex hand-offs, no device
+# call), system compiler
+$(BUILD)/pool_combiner.o: $(CSRC)/pool_combiner.cpp $(CSRC)/pool_combiner.h | $(BUILD)
+	$(CXX) -O2 -fPIC -ffp-contract=off -std=c++17 -Iinclude -fvisibility=hidden -Wall -c $< -o $@
+
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lpthread
 
@@ -110,16 +120,24 @@ $(BUILD)/model_host_check.o: tools/model_host_check.cpp $(HDRS) | $(BUILD)
 $(HOSTCHECK): $(BUILD)/model_host_check.o $(BUILD)/model_host.o $(BUILD)/mf_plan.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
-hostcheck: $(HOSTCHECK)
+# stand-alone CPU check of the flat combiner with a fake launch
+# (tools/pool_combiner_check.cpp gives the sanitizer recipes)
+POOLCHECK := tools/pool_combiner_check
 
-check: $(HOSTCHECK)
+$(POOLCHECK): tools/pool_combiner_check.cpp $(BUILD)/pool_combiner.o $(CSRC)/pool_combiner.h
+	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $< $(BUILD)/pool_combiner.o -lpthread
+
+hostcheck: $(HOSTCHECK) $(POOLCHECK)
+
+check: $(HOSTCHECK) $(POOLCHECK)
 	$(HOSTCHECK)
+	$(POOLCHECK)
 
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK)
+	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK)
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib synth dropin hostcheck oracle clean check

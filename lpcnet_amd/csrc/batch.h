@@ -1,0 +1,189 @@
+/*
+ * batch.h -- what engine.cpp (the batch API) and dropin.cpp (the drop-in
+ * handles over it) share: struct LPCNetBatch, the stream-state helpers and
+ * the partial-batch steps a StatePool runs on its work batch.  Internal to
+ * those two files.
+ */
+#ifndef LPCNET_BATCH_H
+#define LPCNET_BATCH_H
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <functional>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "lpcnet_engine.h"
+#include "lpcnet_mi355x.h"
+#include "model_host.h"
+
+/* LPCNetBatch is the C API's type, outside the namespace its fields come from */
+using namespace lpcnet_mi355x;
+
+#define HIPCHK(x)                                                                          \
+  do {                                                                                     \
+    hipError_t e_ = (x);                                                                   \
+    if (e_ != hipSuccess) {                                                                \
+      set_err(std::string(#x) + ": " + hipGetErrorString(e_));                            \
+      return -1;                                                                           \
+    }                                                                                      \
+  } while (0)
+
+/* ------------------------------------------------------------------------ */
+struct LPCNetBatch {
+  int device = 0;
+  int B = 0;
+  int S = 1;
+  hipStream_t stream = nullptr;
+  /* model */
+  bool have_model = false;
+  int variant = 0;
+  bool sat = false;
+  bool reg = false;
+  int kernel_mode = 0;   /* 0 auto, 1 lockstep sample_kernel, 4 matrix-core mf_kernel, 5 fp32 fp_kernel */
+  ModelConst mc{1.0f, DEFAULT_FEATURES_DELAY, 0}; /* FEATURES_DELAY / LPC_GAMMA / END2END of the model */
+  /* rcpps table of the device activations (RCP_ENTRIES, device form t + kRcpBias);
+   * rcp_custom: not the default Intel table (lpcnet_batch_set_rcp_table) */
+  bool rcp_custom = false;
+  std::vector<uint32_t> rcp_dev;
+  bool mf_ok = false;    /* model fits the matrix-core register tables */
+  bool mf = false;       /* mf_kernel (mode 4) */
+  bool mf2 = false;      /* large batches: mf2_kernel (two staggered 4-stream groups per workgroup) for
+                            launches without preload / trace / stamps */
+  int mfw_g = 3;         /* mfw_kernel's four-stream groups per workgroup (2 or 3) */
+  bool mfw_forced = false; /* LPCNET_MFW=1: mfw_kernel for every launch, however narrow */
+  int cus = 256;           /* compute units of the batch's device */
+  bool mfw = false;      /* wider batches: mfw_kernel (two or three 4-stream groups, dedicated gather /
+                            recurrent / sampler waves; split models in its split form) for the same
+                            launches, models with the default rcpps */
+  bool plan_wide = false; /* the register tables were planned for mfw_kernel (plan class 3) */
+  L2Warm ck_warm{};       /* the chunk kernel's re-tiled weights (deferred LPC warms them) */
+  std::vector<unsigned char> blob; /* the loaded model's blob: replanned when the kernel choice moves */
+  /* The loaded model's host tables (their blob views look into `blob`), kept
+   * until the next load replaces them: 12 to 25 MB.  Returning that memory to
+   * the system at the end of the load costs the sample kernels of this
+   * process about 1 % at 1,024 streams (same box, alternating runs,
+   * profiles/r12: 0.4018 against 0.3976 ms per frame step on the skewed
+   * model, the parent commit 0.3967); the mechanism below that is not known. */
+  std::unique_ptr<HostModel> host;
+  double mf_ga_ops = 0;  /* int8 matrix-core ops per workgroup per sample: the GRU_A recurrent pass */
+  double mf_gb_ops = 0;  /* the GRU_B tiles of both sampler waves */
+  bool fp_ok = false;    /* fp32 model fits the fp_kernel tables */
+  bool fp = false;       /* fp_kernel (mode 5) */
+  int image_bytes = 0;
+  LPCNetModelInfo info{};
+  std::vector<void *> model_bufs;
+  FrameArgs fa{};
+  SampleArgs sa{};
+  int lds_bytes = 0;
+  /* streams */
+  StreamState *d_state = nullptr;
+  float *d_feat = nullptr;
+  short *d_pcm = nullptr;
+  float *d_lpc = nullptr;          /* [LPC_CHUNK][B][NLPC] lpc_from_cepstrum of queued frames */
+  LpcTables *d_lpc_tab = nullptr;
+  /* overlapped multi-frame path (few streams, free CUs): frame kernel f+1 on
+   * fstream beside sample kernel f on stream, outputs double-buffered in
+   * d_cond[f & 1] */
+  hipStream_t fstream = nullptr;
+  FrameCond *d_cond[2] = {nullptr, nullptr};
+  hipEvent_t ev_frame[2] = {nullptr, nullptr}, ev_samp[2] = {nullptr, nullptr}, ev_start = nullptr;
+  bool ev_samp_used[2] = {false, false};
+  hipEvent_t ev_samp_cur[2] = {nullptr, nullptr}; /* the event slot c's reuse waits on */
+  /* chunked multi-frame path (batches above OVERLAP_MAX_STREAMS): the frame
+   * network of up to LPC_CHUNK frames in one chunk_kernel launch, outputs of
+   * frame f in d_chunk[f][B] */
+  FrameCond *d_chunk = nullptr;
+  bool chunking = true;
+  /* per-frame host-I/O path of large batches (synth_first): one frame's
+   * chunk_kernel outputs [B], and pinned staging of the caller's features and
+   * PCM (so both copies are asynchronous, behind one synchronisation) */
+  float *h_io_feat = nullptr;
+  short *h_io_pcm = nullptr;
+  short *d_io_pcm = nullptr; /* h_io_pcm's device address (mapped) */
+  float *d_io_feat = nullptr; /* h_io_feat's device address (mapped) */
+  bool io_feat_vram = false;  /* h_io_feat is host-visible device memory (fine-grained VRAM, large BAR) */
+  float *h_stg_feat = nullptr; /* pinned staging of the caller's own buffers */
+  short *h_stg_pcm = nullptr;
+  hipEvent_t ev_tick = nullptr; /* end of a host-I/O tick (spin-polled) */
+  /* trace */
+  bool trace = false;
+  float *d_trace_logits = nullptr;
+  int *d_trace_exc = nullptr;
+  int trace_N = 0;
+  /* device -> host status word (pinned, mapped): a kernel that aborts sets
+   * STATUS_* bits; every synchronising entry point checks and clears it */
+  int *h_status = nullptr;
+  int *d_status = nullptr;
+  int *d_ck_sync = nullptr; /* [ceil(B / 16)] arrival counters of the sliced one-frame chunk kernel */
+  int spin_limit = FLAG_SPIN_LIMIT_DEFAULT;
+  /* 1.6 kb/s decoder (decode_kernel.hip): the model's ceps codebooks (optional
+   * blob records), packets and decoded features of up to DEC_MAX_PACKETS
+   * packets per stream, the host-I/O path's 4-frame PCM */
+  DecodeArgs da{};
+  bool has_codebooks = false;
+  unsigned char *d_packets = nullptr;
+  float *d_dfeat = nullptr;
+  short *d_dpcm = nullptr;
+  /* PLC prediction network (plc_kernel.hip): optional blob records, tables in
+   * buffers of their own (a re-plan of the synthesis tables keeps them), each
+   * stream's plc_gru1_state | plc_gru2_state outside StreamState (the
+   * synthesis snapshots keep their size), host-I/O staging */
+  bool plc_ok = false;
+  std::string plc_why = "no model loaded"; /* why the PLC calls refuse this batch */
+  PlcArgs pa{};
+  std::vector<void *> plc_bufs;
+  float *d_plc_state = nullptr;
+  float *d_plc_in = nullptr, *d_plc_out = nullptr;
+  unsigned char *d_plc_act = nullptr;
+  /* feature extractor (feat_kernel.hip): no weights, so nothing here depends
+   * on the model; each stream's analysis state in an array of its own, the
+   * constant tables and the host-I/O staging, all allocated by the first
+   * call that extracts features (feat_ensure) */
+  FeatState *d_feat_state = nullptr;
+  FeatTables *d_feat_tab = nullptr;
+  float *d_feat_pcm = nullptr;  /* [B][FRAME] float or short */
+  float *d_feat_out = nullptr;  /* [B][NTF] */
+  unsigned char *d_feat_act = nullptr;
+  /* diagnostics */
+  unsigned long long *d_stamps = nullptr;
+  /* timing */
+  int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
+  std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
+  std::vector<hipEvent_t> ev_pairs[4]; /* sample kernel, frame kernel, PLC predictor, feature extractor */
+  std::vector<int> ev_frames[4];    /* frames covered by each pair */
+  std::vector<hipEvent_t> ev_free;
+  /* lower bound of every stream's frame_count (lpcnet.c:119) before the next
+   * frame: the multi-frame sample launches start where no stream can still
+   * be inside its first `delay` (FEATURES_DELAY) frames */
+  int min_fc = 0;
+  void frames_done(int n) { min_fc = min_fc >= 1000 ? min_fc : std::min(min_fc + n, 1000); }
+  int set_device() { return hipSetDevice(device) == hipSuccess ? 0 : -1; }
+};
+
+namespace lpcnet_mi355x {
+
+/* Work a caller enqueues on b->stream after a step's kernels, before its one
+ * synchronisation (the drop-in pool's state scatter). */
+using PreSync = std::function<int()>;
+
+/* a stream's state after lpcnet_init / lpcnet_reset_signal; whether a
+ * snapshot is one this engine can have produced (set_err when not) */
+void host_reset_state(StreamState &s);
+void reset_signal(StreamState &s);
+bool snapshot_ok(const void *buf);
+
+/* One step for the first nB streams of a batch, host I/O, `pre` queued
+ * behind its kernels (engine.cpp, at each definition).  staged: the caller
+ * has queued the features / preload copies on b->stream already. */
+int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm, int N, int preload,
+                const PreSync &pre = PreSync(), bool staged = false);
+int tail_first(LPCNetBatch *b, int nB, short *pcm, int N, int preload, const PreSync &pre = PreSync());
+int frame_first(LPCNetBatch *b, int nB, const float *features, bool keep_cond, const PreSync &pre = PreSync());
+int decode_first(LPCNetBatch *b, int nB, const unsigned char *packets, short *pcm, const PreSync &pre = PreSync());
+
+}  // namespace lpcnet_mi355x
+
+#endif

@@ -357,7 +357,7 @@ int launch_cond_copy(const StreamState *st, FrameCond *cond, int nstreams, void 
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-/* Stream-state moves of the shared drop-in pool (engine.cpp StatePool):
+/* Stream-state moves of the shared drop-in pool (dropin.cpp StatePool):
  * dst[dmap ? dmap[k] : k] = src[smap ? smap[k] : k] for k < n, one
  * workgroup per state, 16 bytes per thread. */
 __global__ __launch_bounds__(256) void state_copy_kernel(StreamState *dst, const StreamState *src, const int *dmap,

@@ -1,7 +1,7 @@
 """The drop-in API (include/lpcnet.h) shared across handles: every
 LPCNetState bound to the same model on one device is a slot of one pool (one
 device model, one work batch), and concurrent lpcnet_synthesize calls on
-different handles coalesce into one launch (engine.cpp StatePool).  Each
+different handles coalesce into one launch (dropin.cpp StatePool).  Each
 handle must still produce exactly its own stream's reference PCM."""
 import ctypes as C
 import threading
@@ -204,7 +204,7 @@ def test_three_request_shapes_interleaved_match_oracle(require_gpu):
 
 
 def test_placement_spreads_handles_and_matches_oracle(require_gpu, monkeypatch):
-    """Drop-in placement (engine.cpp place_new_handle): with two placements
+    """Drop-in placement (dropin.cpp place_new_handle): with two placements
     of the one GPU (lpcnet_mi355x_set_placement([0, 0]), what
     LPCNET_DEVICES=0,0 sets), 16 handles split 8 / 8 by handle count, each
     placement runs its own pool, 16 threads at once, and every handle's PCM

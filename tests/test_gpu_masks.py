@@ -5,7 +5,7 @@ trained model's block rows can be far longer than the mean (the synthetic
 must run bit-exactly and without falling off the fast kernels:
 
 * int8: mf_kernel splits rows longer than its own cap into pieces hosted by
-  other lane groups, whose int32 partial sums merge exactly (engine.cpp
+  other lane groups, whose int32 partial sums merge exactly (mf_plan.cpp
   mf_plan); LPCNET_MF_FORCE_SPLIT exercises the same machinery on the
   default model against the golden fixture;
 * saturating int8 / fp32 with long rows: the lockstep kernel with its
