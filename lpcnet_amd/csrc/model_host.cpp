@@ -396,7 +396,7 @@ struct Image {
     align16();
     size_t off = img.size();
     img.resize(off + n);
-    memcpy(&img[off], p, n);
+    if (n) memcpy(img.data() + off, p, n); /* an empty section (a wave without blocks in a gate) has no source */
     return off;
   }
 };
@@ -636,6 +636,10 @@ void build_matrix_core_tables(const Blob &B, const ModelBuildOpts &opts, const L
   const int8_t *wa = (const int8_t *)B.ga.w;
   mf_tables(B.ga.blocks, B.ga.first, wa, plan, H.mf);
   sa.mf_split = plan.split ? 1 : 0;
+  for (int g = 0; g < 3; g++) {
+    H.mf_own[g] = plan.own[g];
+    H.mf_pieces[g] = (int)plan.pieces[g].size();
+  }
   for (int w = 0; w < SAMPLE_WAVES; w++) {
     sa.mf_nzr[w] = plan.nzr[w];
     sa.mf_nh[w] = plan.nh[w];

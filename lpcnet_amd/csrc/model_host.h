@@ -110,6 +110,7 @@ struct HostModel {
   std::vector<int> ga_wsum, gb_wsum;
   std::vector<unsigned char> img;
   MfTab mf;
+  int mf_own[3] = {}, mf_pieces[3] = {}; /* the plan behind mf: own caps in blocks and hosted pieces per gate (checks) */
   MfwSplitTab mfw;
   std::vector<uint32_t> mf_gb;
   std::vector<float> mf_emb[3], mfw_emb[3]; /* embedding tables in mf.units / mfw.units lane order */

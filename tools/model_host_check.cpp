@@ -5,7 +5,12 @@
  *
  *   make check        (builds and runs tools/model_host_check)
  *
- * For the int8 synthetic models (default, skewed: split plans) in every plan
+ *   tools/model_host_check FILE...   (the same on weight blobs; one "plan"
+ *                                     line per plan on stdout: the planner's
+ *                                     verdict, caps, pieces, groups per wave)
+ *
+ * For the int8 synthetic models (default, skewed: split plans; seed 1, then
+ * the default and skewed models of seeds 2..8) in every plan
  * class (1, 512, 1024, 2048 streams; 8192 streams planned for the wide
  * kernel), and again with every plan forced to split, it decodes
  *   - mf / mf_unit / mf_frow (own and hosted regions, through the slots'
@@ -16,7 +21,10 @@
  * its column, in a row whose partial sum reaches the right unit.  It also
  * checks the slot budgets of every wave (4 (nzr + nfzr) <= MF_ZMAX,
  * 4 (nh + nfh) <= MF_HMAX), that a lane group hosts at most one piece per
- * gate, and that the dense GRU_B tiles decode to the blob's GRU_B.
+ * gate, that a gate without pieces has no merge flag and no hosted row, that
+ * the wide split form exists exactly when the mask allows it, and that the
+ * dense GRU_B tiles decode to the blob's GRU_B.  A model the planner
+ * declines (the lockstep kernel runs it) is counted, not failed.
  *
  * Under AddressSanitizer and UBSan (host code only):
  *
@@ -115,6 +123,9 @@ static void check_mf(const HostModel &H, const Mat &R, const char *tag)
         const int nown = 4 * (g < 2 ? sa.mf_nzr[w] : sa.mf_nh[w]), nfor = 4 * (g < 2 ? sa.mf_nfzr[w] : sa.mf_nfh[w]);
         const int fr = H.mf.frow[((size_t)g * SAMPLE_WAVES + w) * 64 + l], target = fr & 0xFFFF;
         if (fr >> 16) merged[g].insert(unit / 8);
+        /* a gate without pieces: no lane merges, no lane hosts (z and r share their group counts, so a
+         * wave can carry hosted slots of one for the other's pieces: zero weights, no row) */
+        if (H.mf_pieces[g] == 0) CHECK(fr == NA, "%s: wave %d lane %d gate %d entry %#x in a gate without pieces", tag, w, l, g, fr);
         add_slots(wtab, l, gate_base(g), nown, g * NA + unit, D, tag);
         /* one piece per lane group and gate: its 8 lanes carry rows 8 u .. 8 u + 7 of one unit block u, or none */
         const int t0 = H.mf.frow[((size_t)g * SAMPLE_WAVES + w) * 64 + (l & ~7)] & 0xFFFF;
@@ -122,6 +133,8 @@ static void check_mf(const HostModel &H, const Mat &R, const char *tag)
               tag, w, l, g, target);
         if (target < NA) hosted[g].insert(target / 8);
         add_slots(wtab, l, gate_base(g) + nown, nfor, target < NA ? g * NA + target : -1, D, tag);
+        /* a wave with no group at all in a gate (used 0: the kernels' runtime-count default) has only
+         * zero words in that gate's slots: this covers it */
         check_unused(wtab, l, g, nown + nfor, tag);
       }
     }
@@ -220,63 +233,144 @@ static void check_gru_b(const HostModel &H, const char *tag)
   CHECK(Drec == Rrec, "%s: GRU_B recurrent tiles differ from the blob", tag);
 }
 
-int main(void)
+/* mfw_kernel's split form, from the mask alone: it exists exactly when every
+ * gate's blocks beyond the register caps (MF_ZMAX / MF_ZMAX / MF_HMAX per
+ * row) make at most 16 pieces of at most a cap each (one per lane group of
+ * the two host waves) over at most 16 unit blocks (the part area's rows) */
+static bool wide_split_exists(const GruASparse &A)
 {
-  static const struct { const char *name; int flags; bool mf; } models[] = {
-      {"int8", 0, true}, {"int8_saturating", 1, false}, {"int8_skewed", 2, true}};
+  constexpr int NUB = NA / 8;
+  for (int g = 0; g < 3; g++) {
+    const int cap = g < 2 ? MF_ZMAX : MF_HMAX;
+    int pieces = 0, units = 0;
+    for (int u = 0; u < NUB; u++) {
+      const int beyond = (int)A.blocks[g * NUB + u].size() - cap;
+      if (beyond <= 0) continue;
+      pieces += (beyond + cap - 1) / cap;
+      units++;
+    }
+    if (pieces > 8 * MFW_H_WAVES || units > MFW_PART_ROWS / 8) return false;
+  }
+  return true;
+}
+
+static int plans, split_plans, wide_plans, declined;
+
+/* One blob in every plan class, as planned and with every plan forced to
+ * split.  mf: 1 / 0 = the planner must take / decline the model, -1 = either
+ * (a declined plan is counted, the lockstep kernel runs such a model).
+ * report: one "plan" line per plan on stdout. */
+static void check_model(const char *name, const unsigned char *blob, int n, int mf, bool report)
+{
   static const struct { int streams; bool wide; } classes[] = {{1, false}, {512, false}, {1024, false}, {2048, false}, {8192, true}};
+  /* the matrix the tables must decode to */
+  std::vector<Arr> L;
+  GruASparse A;
+  if (!parse_blob(L, blob, n) || parse_gru_a(L, A)) {
+    CHECK(false, "%s: blob does not parse (%s)", name, last_err().c_str());
+    return;
+  }
+  const bool int8 = A.variant == LPCNET_VARIANT_INT8;
+  Mat R;
+  if (int8) {
+    R.assign((size_t)GA_ROWS * NA, 0);
+    for (int rb = 0; rb < GA_ROWS / 8; rb++)
+      for (int t = 0; t < (int)A.blocks[rb].size(); t++)
+        for (int r = 0; r < 8; r++)
+          for (int c = 0; c < 4; c++)
+            R[(size_t)(rb * 8 + r) * NA + A.blocks[rb][t] + c] += ((const int8_t *)A.w)[32 * (A.first[rb] + t) + 4 * r + c];
+  }
+  for (int force = 0; force < 2; force++) {
+    if (force) setenv("LPCNET_MF_FORCE_SPLIT", "1", 1);
+    else unsetenv("LPCNET_MF_FORCE_SPLIT");
+    for (const auto &c : classes) {
+      char tag[300];
+      snprintf(tag, sizeof tag, "%s/%d%s%s", name, c.streams, c.wide ? "/wide" : "", force ? "/forced split" : "");
+      ModelBuildOpts opts;
+      opts.streams = c.streams;
+      opts.wide = c.wide;
+      HostModel H;
+      if (build_host_model(blob, n, opts, H)) {
+        CHECK(false, "%s: build failed: %s", tag, last_err().c_str());
+        continue;
+      }
+      if (report) {
+        printf("plan %s: variant %d may_saturate %d mf_ok %d fp_ok %d fp_long %d lockstep_streams %d", tag, H.variant, H.sat, H.mf_ok,
+               H.fp_ok, H.fp_long, H.S);
+        if (H.mf_ok) {
+          printf(" split %d wide_split %d own %d %d %d pieces %d %d %d groups", H.sa.mf_split, H.sa.mfw_split, H.mf_own[0], H.mf_own[1],
+                 H.mf_own[2], H.mf_pieces[0], H.mf_pieces[1], H.mf_pieces[2]);
+          for (int w = 0; w < SAMPLE_WAVES; w++) printf(" (%d %d %d %d)", H.sa.mf_nzr[w], H.sa.mf_nfzr[w], H.sa.mf_nh[w], H.sa.mf_nfh[w]);
+        }
+        printf("\n");
+      }
+      CHECK(int8 || !H.mf_ok, "%s: matrix-core tables of an fp32 model", tag);
+      if (mf >= 0) CHECK(H.mf_ok == (mf != 0), "%s: matrix-core tables %d", tag, H.mf_ok);
+      if (!H.mf_ok) {
+        declined++;
+        continue;
+      }
+      CHECK(!force || H.sa.mf_split, "%s: plan not split", tag);
+      CHECK(H.sa.mfw_split == (H.sa.mf_split && c.wide && wide_split_exists(A) ? 1 : 0), "%s: wide split form %d", tag, H.sa.mfw_split);
+      check_mf(H, R, tag);
+      if (H.sa.mfw_split) check_mfw(H, R, tag);
+      check_gru_b(H, tag);
+      plans++;
+      split_plans += H.sa.mf_split;
+      wide_plans += H.sa.mfw_split;
+    }
+  }
+  unsetenv("LPCNET_MF_FORCE_SPLIT");
+}
+
+static bool read_file(const char *path, std::vector<unsigned char> &out)
+{
+  FILE *f = fopen(path, "rb");
+  if (!f) return false;
+  unsigned char buf[1 << 16];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + n);
+  fclose(f);
+  return true;
+}
+
+/* model_host_check            the synthetic int8 models of seed 1 (default, saturating, skewed), then the default and
+ *                             skewed models of seeds 2..8
+ * model_host_check FILE...    the given blobs, with one "plan" line per plan class on stdout */
+int main(int argc, char **argv)
+{
   static const char *const hooks[] = {"LPCNET_MF_ITERS", "LPCNET_MF_SIMD_W", "LPCNET_MF_HOSTED_F", "LPCNET_MF_PIECE_W",
                                       "LPCNET_MF_CAPS", "LPCNET_MF_FORCE_SPLIT", "LPCNET_NO_MFMA", "LPCNET_NO_MFW_SPLIT",
                                       "LPCNET_RCP", "LPCNET_VERBOSE"};
   for (const char *h : hooks) unsetenv(h);
-  int plans = 0, split = 0, wide = 0;
-  for (int force = 0; force < 2; force++) {
-    if (force) setenv("LPCNET_MF_FORCE_SPLIT", "1", 1);
-    for (const auto &m : models) {
-      const int n = lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, m.flags, nullptr, 0);
-      std::vector<unsigned char> blob(n);
-      lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, m.flags, blob.data(), n);
-      /* the matrix the tables must decode to */
-      std::vector<Arr> L;
-      GruASparse A;
-      if (!parse_blob(L, blob.data(), n) || parse_gru_a(L, A) || A.variant != LPCNET_VARIANT_INT8) {
-        CHECK(false, "%s: synthetic blob does not parse (%s)", m.name, last_err().c_str());
-        continue;
-      }
-      Mat R((size_t)GA_ROWS * NA, 0);
-      for (int rb = 0; rb < GA_ROWS / 8; rb++)
-        for (int t = 0; t < (int)A.blocks[rb].size(); t++)
-          for (int r = 0; r < 8; r++)
-            for (int c = 0; c < 4; c++)
-              R[(size_t)(rb * 8 + r) * NA + A.blocks[rb][t] + c] += ((const int8_t *)A.w)[32 * (A.first[rb] + t) + 4 * r + c];
-      for (const auto &c : classes) {
-        char tag[96];
-        snprintf(tag, sizeof tag, "%s/%d%s%s", m.name, c.streams, c.wide ? "/wide" : "", force ? "/forced split" : "");
-        ModelBuildOpts opts;
-        opts.streams = c.streams;
-        opts.wide = c.wide;
-        HostModel H;
-        if (build_host_model(blob.data(), n, opts, H)) {
-          CHECK(false, "%s: build failed: %s", tag, last_err().c_str());
-          continue;
-        }
-        CHECK(H.mf_ok == m.mf, "%s: matrix-core tables %d", tag, H.mf_ok);
-        if (!H.mf_ok) continue;
-        CHECK(!force || H.sa.mf_split, "%s: plan not split", tag);
-        CHECK(H.sa.mfw_split == (H.sa.mf_split && c.wide ? 1 : 0), "%s: wide split form %d", tag, H.sa.mfw_split);
-        check_mf(H, R, tag);
-        if (H.sa.mfw_split) check_mfw(H, R, tag);
-        check_gru_b(H, tag);
-        plans++;
-        split += H.sa.mf_split;
-        wide += H.sa.mfw_split;
-      }
+  for (int i = 1; i < argc; i++) {
+    std::vector<unsigned char> blob;
+    if (!read_file(argv[i], blob)) {
+      CHECK(false, "%s: cannot read", argv[i]);
+      continue;
     }
+    check_model(argv[i], blob.data(), (int)blob.size(), -1, true);
+  }
+  if (argc < 2) {
+    /* a skewed model of another seed may or may not fit the register tables split: either is right */
+    static const struct { const char *name; int flags; int mf, mf_other_seeds; } models[] = {
+        {"int8", 0, 1, 1}, {"int8_saturating", 1, 0, -2}, {"int8_skewed", 2, 1, -1}};
+    for (unsigned seed = 1; seed <= 8; seed++)
+      for (const auto &m : models) {
+        if (seed > 1 && m.mf_other_seeds < -1) continue;
+        const int n = lpcnet_mi355x_synthetic_model(seed, LPCNET_VARIANT_INT8, m.flags, nullptr, 0);
+        std::vector<unsigned char> blob(n);
+        lpcnet_mi355x_synthetic_model(seed, LPCNET_VARIANT_INT8, m.flags, blob.data(), n);
+        char name[64];
+        snprintf(name, sizeof name, "%s/seed %u", m.name, seed);
+        check_model(name, blob.data(), n, seed == 1 ? m.mf : m.mf_other_seeds, false);
+      }
   }
   if (fails) {
     fprintf(stderr, "model_host_check: %d checks failed\n", fails);
     return 1;
   }
-  printf("model_host_check ok (%d plans decoded, %d split, %d with the wide split form)\n", plans, split, wide);
+  printf("model_host_check ok (%d plans decoded, %d split, %d with the wide split form; %d declined by the planner)\n", plans,
+         split_plans, wide_plans, declined);
   return 0;
 }
