@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/enc_features.npz (run where oracle/_ref is built).
+"""Generates tests/golden/enc_features.npz and
+tests/golden/enc_features_edge.npz (run where oracle/_ref is built).
 
 Five int16 signals x 12 frames and the [12][36] features of each, computed by
 tests/enc_ref.py: the reference's own compiled freq.c / pitch.c
@@ -11,6 +12,11 @@ lpcnet_enc.c's single-frame path.
   silence    all zero (every Viterbi maximum tied: strict > decides)
   noise      uniform noise in [-3000, 3000]
   square100  a full-scale (+-32767) square wave of period 100
+
+enc_features_edge.npz: the 23 int16 and 4 float32 edge-case signals of
+tests/feat_signals.py x 24 frames, with the features of every frame, the
+SHA-256 of EncRef.state_bytes() after every frame and the state after the
+last one.
 
 Usage: python3 tests/golden/make_enc_golden.py
 """
@@ -24,6 +30,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import enc_ref as E  # noqa: E402
+import feat_signals as FS  # noqa: E402
 
 NFRAMES = 12
 N = NFRAMES * E.FRAME_SIZE
@@ -60,5 +67,30 @@ def main():
         print("  %-10s pitch %s corr %s" % (n, np.round(f[-3:, 18], 2), np.round(f[-3:, 19], 3)))
 
 
+def edge_arrays() -> dict:
+    """What enc_features_edge.npz holds (tests/feat_signals.py: fixture())."""
+    pcm_i16, pcm_f32 = FS.make_all()
+    feats, digests, states = [], [], []
+    for pcm in list(pcm_i16) + list(pcm_f32):
+        r = E.EncRef()
+        f, d = [], []
+        for frame in pcm:
+            f.append(r.frame(frame))
+            d.append(np.frombuffer(FS.digest(r.state_bytes()), np.uint8))
+        feats.append(np.stack(f))
+        digests.append(np.stack(d))
+        states.append(np.frombuffer(r.state_bytes(), np.uint8))
+    return dict(pcm_i16=pcm_i16, pcm_f32=pcm_f32, features=np.stack(feats), digests=np.stack(digests),
+                state=np.stack(states), names=np.array(FS.NAMES))
+
+
+def main_edge():
+    a = edge_arrays()
+    assert np.isfinite(a["features"]).all()
+    np.savez_compressed(FS.GOLDEN, **a)
+    print("wrote %s: %d signals, %d bytes" % (FS.GOLDEN, len(FS.NAMES), os.path.getsize(FS.GOLDEN)))
+
+
 if __name__ == "__main__":
     main()
+    main_edge()
