@@ -318,6 +318,35 @@ LPCNET_EXPORT int lpcnet_mi355x_validate_model(const unsigned char *data, int le
  * of entries written (60; cap must hold them) or -1. */
 LPCNET_EXPORT int lpcnet_mi355x_model_digest(const unsigned char *data, int len, int streams, int cus, int wide, uint64_t *out,
                                              int cap);
+/* Host-only: which sample kernel and which frame path a batch of `streams`
+ * streams of the blob takes on a device of `cus` compute units (0: as many
+ * as the current HIP device has, the only case that asks a device), with
+ * `kernel_mode` (lpcnet_batch_set_kernel), a custom rcpps table or not, and
+ * the current environment (LPCNET_MF2, LPCNET_MFW, LPCNET_MFW_G,
+ * LPCNET_NO_CHUNK, LPCNET_NO_MULTIFRAME, LPCNET_NO_OVERLAP, LPCNET_LPC_EAGER,
+ * LPCNET_NO_DIRECT_PCM).  The host model is built as a load builds it.
+ *   plan[LPCNET_CHOICE_PLAN]: base kernel (0 lockstep sample_kernel, 1
+ *     mf_kernel, 4 fp_kernel), mf2, mfw, mfw_g, mfw_forced, plan_wide (the
+ *     plan class the register tables were built for), rcp_hw, then
+ *     LPCNetModelInfo's quad_path, streams_per_workgroup, lds_bytes and
+ *     mfma_ops_per_group_sample (as an integer), then whether the batch-level
+ *     predicate asks for the wide plan class and whether the model has
+ *     matrix-core tables at all (only then does a batch re-plan);
+ *   launches [nlaunches][4] = (streams of the launch, preload, trace,
+ *     stamps) -> launch_out [nlaunches][2] = (kernel: 0 lockstep, 1
+ *     mf_kernel, 2 mf2_kernel, 3 mfw_kernel, 4 fp_kernel; its PCM store is
+ *     coalesced, so a host-I/O tick may store PCM straight to host memory);
+ *   calls [ncalls][10] = (nframes, N, streams of the call, preload, frame
+ *     chunking, the batch has a second queue, trace, stamps, features_delay,
+ *     end2end) -> call_out [ncalls][5] = (lpcnet_batch_synthesize_frames:
+ *     multi-frame sample launches, overlapped frame kernels, chunked frame
+ *     network; lpcnet_batch_synthesize: the one-frame chunked form, deferred
+ *     LPC).
+ * Returns the CU count planned for, or -1 (lpcnet_mi355x_last_error). */
+#define LPCNET_CHOICE_PLAN 13
+LPCNET_EXPORT int lpcnet_mi355x_kernel_choice(const unsigned char *data, int len, int streams, int cus, int kernel_mode,
+                                              int rcp_custom, int *plan, const int *launches, int nlaunches, int *launch_out,
+                                              const int *calls, int ncalls, int *call_out);
 /* Number of visible HIP devices (0 on a machine without GPU). */
 LPCNET_EXPORT int lpcnet_mi355x_device_count(void);
 /* Host-only view of the GRU_A plans a blob (data, len) gets on a wide batch

@@ -35,29 +35,19 @@ using namespace lpcnet_mi355x;
 struct LPCNetBatch {
   int device = 0;
   int B = 0;
-  int S = 1;
   hipStream_t stream = nullptr;
   /* model */
   bool have_model = false;
   int variant = 0;
   bool sat = false;
-  bool reg = false;
   int kernel_mode = 0;   /* 0 auto, 1 lockstep sample_kernel, 4 matrix-core mf_kernel, 5 fp32 fp_kernel */
   ModelConst mc{1.0f, DEFAULT_FEATURES_DELAY, 0}; /* FEATURES_DELAY / LPC_GAMMA / END2END of the model */
   /* rcpps table of the device activations (RCP_ENTRIES, device form t + kRcpBias);
    * rcp_custom: not the default Intel table (lpcnet_batch_set_rcp_table) */
   bool rcp_custom = false;
   std::vector<uint32_t> rcp_dev;
-  bool mf_ok = false;    /* model fits the matrix-core register tables */
-  bool mf = false;       /* mf_kernel (mode 4) */
-  bool mf2 = false;      /* large batches: mf2_kernel (two staggered 4-stream groups per workgroup) for
-                            launches without preload / trace / stamps */
-  int mfw_g = 3;         /* mfw_kernel's four-stream groups per workgroup (2 or 3) */
-  bool mfw_forced = false; /* LPCNET_MFW=1: mfw_kernel for every launch, however narrow */
-  int cus = 256;           /* compute units of the batch's device */
-  bool mfw = false;      /* wider batches: mfw_kernel (two or three 4-stream groups, dedicated gather /
-                            recurrent / sampler waves; split models in its split form) for the same
-                            launches, models with the default rcpps */
+  ModelCaps caps{};      /* what the kernel choice takes from the model (kernel_choice.h) */
+  SamplePlan plan{};     /* the batch's sample kernels: plan_sample_kernels, per launch kernel_for_launch */
   bool plan_wide = false; /* the register tables were planned for mfw_kernel (plan class 3) */
   L2Warm ck_warm{};       /* the chunk kernel's re-tiled weights (deferred LPC warms them) */
   std::vector<unsigned char> blob; /* the loaded model's blob: replanned when the kernel choice moves */
@@ -68,16 +58,11 @@ struct LPCNetBatch {
    * profiles/r12: 0.4018 against 0.3976 ms per frame step on the skewed
    * model, the parent commit 0.3967); the mechanism below that is not known. */
   std::unique_ptr<HostModel> host;
-  double mf_ga_ops = 0;  /* int8 matrix-core ops per workgroup per sample: the GRU_A recurrent pass */
-  double mf_gb_ops = 0;  /* the GRU_B tiles of both sampler waves */
-  bool fp_ok = false;    /* fp32 model fits the fp_kernel tables */
-  bool fp = false;       /* fp_kernel (mode 5) */
   int image_bytes = 0;
   LPCNetModelInfo info{};
   std::vector<void *> model_bufs;
   FrameArgs fa{};
   SampleArgs sa{};
-  int lds_bytes = 0;
   /* streams */
   StreamState *d_state = nullptr;
   float *d_feat = nullptr;

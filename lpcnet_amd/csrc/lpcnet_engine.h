@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_choice.h" /* OVERLAP_MAX_STREAMS, CHUNK_MIN_FRAMES, MF2_MIN_STREAMS, mfw_groups */
+
 namespace lpcnet_mi355x {
 
 /* Default model dimensions (training_tf2/lpcnet.py:312-325; the reference
@@ -128,7 +130,6 @@ constexpr int IMG_VAR = IMG_FCF + 512 * 4;       /* start of the variable sectio
 constexpr int ZC_FEAT_MAX = 4096; /* host-I/O ticks up to this size read the features from mapped host memory */
 constexpr int TICK_SPIN_MS = 20;  /* a host-I/O tick polls its end this long before a blocking wait */
 constexpr int TICK_POLL_PAUSE = 0; /* x86 pause instructions between two polls */
-constexpr int OVERLAP_MAX_STREAMS = 128; /* batches up to this size get the overlapped multi-frame path (sample + frame workgroups fit the 256 CUs) */
 
 struct alignas(16) FrameCond {
   float gru_a_cond[GA_ROWS];
@@ -355,7 +356,6 @@ int launch_sample(const SampleArgs &a, int S, int variant, int sat, int reg, int
 /* Frame network of up to LPC_CHUNK frames in one launch (chunk_kernel.hip):
  * f32 matrix cores, 64 (stream, frame) columns per workgroup. */
 int launch_chunk(const FrameArgs &a, void *stream);
-constexpr int CHUNK_MIN_FRAMES = 4; /* shorter runs use the per-frame kernel */
 /* Matrix-core kernel (non-saturating int8 models within the MF_* limits):
  * GRU_A recurrent product on v_mfma_i32_4x4x4_16b_i8 in the GRU_A waves,
  * GRU_B products on v_mfma_i32_16x16x64_i8 in the sampler waves, two
@@ -364,7 +364,6 @@ int mf_lds_bytes(int S, int split);
 int launch_mf(const SampleArgs &a, int S, int lds_bytes, void *stream);
 /* Large batches: two groups of S streams per workgroup, half a sample
  * apart (mf2_kernel.hip); no preload / trace / stamps. */
-constexpr int MF2_MIN_STREAMS = 2048; /* automatic choice of mf2_kernel from this batch size */
 int mf2_lds_bytes(int S, int split);
 int launch_mf2(const SampleArgs &a, int S, void *stream);
 /* wide-batch kernel (mfw_kernel.hip): 2 or 3 four-stream groups per
@@ -372,16 +371,7 @@ int launch_mf2(const SampleArgs &a, int S, void *stream);
  * sampler waves (split models: two groups, 1,024 threads with two host
  * waves); int8 models with the default (Intel) rcpps, no preload / trace /
  * stamps (-1 otherwise) */
-/* mfw_kernel runs in rounds of one workgroup per CU.  Per stream at whole
- * rounds (24,576 streams, same box, profiles/r05): two groups 7.07 ms per
- * frame, three 7.36 (per-phase time 1.04x), mf2_kernel 8.02 -- so two
- * groups replace mf2_kernel wherever both apply (same 8-stream rounds), and
- * three groups are taken where their 12-stream rounds save more than the 4 %
- * (3,072 streams: one round against two).  Above 4 streams per CU only:
- * below, mf_kernel's one-group latency wins. */
-constexpr double MFW_G3_PHASE = 1.08; /* 1.04 before two groups took the LDS rcpps table (-3.4 %) */
-/* 0 (batch within one mf_kernel<4> round), 2 or 3 */
-int mfw_groups(int B, int cus);
+/* group count and selection: kernel_choice.h (mfw_groups, MFW_G3_PHASE) */
 int mfw_lds_bytes(int groups, int split = 0);
 int launch_mfw(const SampleArgs &a, int groups, void *stream);
 /* fp32 latency kernel: one stream per workgroup, LDS flags instead of

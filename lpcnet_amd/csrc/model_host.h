@@ -64,7 +64,7 @@ int parse_gru_a(const std::vector<Arr> &L, GruASparse &A);
  * where it needs them. */
 struct ModelBuildOpts {
   int streams = 1;      /* the batch size: plan class and streams per workgroup */
-  bool wide = false;    /* the batch will run mfw_kernel (engine.cpp mfw_planned): plan class 3 and,
+  bool wide = false;    /* the batch will run mfw_kernel (kernel_choice.cpp plans_wide): plan class 3 and,
                            for split models, the wide split tables */
   /* replan: the batch's own blob again, for new register tables only: what
    * the caller set since the load -- the model constants, the rcpps table --
