@@ -14,10 +14,10 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
@@ -72,6 +72,10 @@ $(BUILD)/engine.o: $(CSRC)/engine.cpp $(HDRS) | $(BUILD)
 $(BUILD)/dropin.o: $(CSRC)/dropin.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
+# the PLC, feature and LPC calls beside synthesis, on the engine's batch (batch.h)
+$(BUILD)/side_calls.o: $(CSRC)/side_calls.cpp $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
 $(BUILD)/lpc_kernel.o: $(CSRC)/lpc_kernel.hip $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
@@ -91,11 +95,15 @@ $(BUILD)/feat_kernel.o: $(CSRC)/feat_kernel.hip $(HDRS) | $(BUILD)
 $(BUILD)/model_gen.o: $(CSRC)/model_gen.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
-# host-only code: the GRU_A planner and the blob -> HostModel ingest
+# host-only code: the GRU_A planner, the blob -> HostModel ingest and the
+# tables beside the synthesis model (PLC predictor, LPC, feature extractor)
 $(BUILD)/mf_plan.o: $(CSRC)/mf_plan.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
 $(BUILD)/model_host.o: $(CSRC)/model_host.cpp $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
+$(BUILD)/side_tables.o: $(CSRC)/side_tables.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
 # host-only: the CPU's own rcpps (x86 SSE), system compiler
@@ -122,7 +130,7 @@ HOSTCHECK := tools/model_host_check
 $(BUILD)/model_host_check.o: tools/model_host_check.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
-$(HOSTCHECK): $(BUILD)/model_host_check.o $(BUILD)/model_host.o $(BUILD)/mf_plan.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o
+$(HOSTCHECK): $(BUILD)/model_host_check.o $(BUILD)/model_host.o $(BUILD)/side_tables.o $(BUILD)/mf_plan.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
 # stand-alone CPU check of the flat combiner with a fake launch

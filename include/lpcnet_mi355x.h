@@ -318,6 +318,17 @@ LPCNET_EXPORT int lpcnet_mi355x_validate_model(const unsigned char *data, int le
  * of entries written (60; cap must hold them) or -1. */
 LPCNET_EXPORT int lpcnet_mi355x_model_digest(const unsigned char *data, int len, int streams, int cus, int wide, uint64_t *out,
                                              int cap);
+/* Host-only digests of the tables beside the synthesis model, one FNV-1a-64
+ * per entry:
+ *   [0..9]   the PLC predictor's device tables, as uploaded: d1_w, d1_b,
+ *            g1_in, g1_rec, g1_seed, g2_in, g2_rec, g2_seed, out_w, out_b
+ *            (0 each when data is NULL or the blob has no usable PLC records);
+ *   [10]     the lpc_from_cepstrum tables (lpc_kernel.hip);
+ *   [11]     the feature extractor's tables (feat_kernel.hip);
+ *   [12..15] not digests: the PLC dims as lpcnet_mi355x_plc_dims gives them
+ *            (0 each without usable PLC records).
+ * Returns the number of entries written (16; cap must hold them) or -1. */
+LPCNET_EXPORT int lpcnet_mi355x_side_digest(const unsigned char *data, int len, uint64_t *out, int cap);
 /* Host-only: which sample kernel and which frame path a batch of `streams`
  * streams of the blob takes on a device of `cus` compute units (0: as many
  * as the current HIP device has, the only case that asks a device), with

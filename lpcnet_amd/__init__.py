@@ -123,6 +123,7 @@ def _load():
         "lpcnet_batch_decode_frames": (i, [vp, vp, vp, i]),
         # PLC prediction network (compute_plc_pred, lpcnet_plc.c:135-145)
         "lpcnet_mi355x_plc_dims": (i, [C.c_char_p, i, vp]),
+        "lpcnet_mi355x_side_digest": (i, [C.c_char_p, i, vp, i]),
         "lpcnet_batch_plc_info": (i, [vp, vp]),
         "lpcnet_batch_plc_predict": (i, [vp, vp, vp, vp]),
         "lpcnet_batch_plc_predict_device": (i, [vp, vp, vp, vp]),
@@ -234,6 +235,16 @@ def plc_dims(blob: bytes) -> tuple[int, int, int, int]:
     if lib.lpcnet_mi355x_plc_dims(blob, len(blob), d) != 0:
         raise LPCNetError(last_error())
     return tuple(d)
+
+
+def side_digest(blob: bytes | None) -> list[int]:
+    """lpcnet_mi355x_side_digest: FNV-1a-64 of the ten PLC tables of a blob (0
+    without usable PLC records, or for None), of the LPC and feature-extractor
+    tables, then the four PLC dims (host only)."""
+    out = (C.c_uint64 * 16)()
+    if lib.lpcnet_mi355x_side_digest(blob, len(blob) if blob else 0, out, 16) != 16:
+        raise LPCNetError(last_error())
+    return list(out)
 
 
 def with_model_constants(blob: bytes, lpc_gamma: float | None = None, features_delay: int | None = None,

@@ -1,8 +1,10 @@
 /*
- * batch.h -- what engine.cpp (the batch API) and dropin.cpp (the drop-in
- * handles over it) share: struct LPCNetBatch, the stream-state helpers and
- * the partial-batch steps a StatePool runs on its work batch.  Internal to
- * those two files.
+ * batch.h -- what engine.cpp (the batch API), dropin.cpp (the drop-in
+ * handles over it) and side_calls.cpp (the PLC, feature and LPC calls beside
+ * synthesis) share: struct LPCNetBatch, the stream-state helpers, the timed
+ * regions, the partial-batch steps a StatePool runs on its work batch and
+ * what a batch's load and destruction call of side_calls.cpp.  Internal to
+ * those three files.
  */
 #ifndef LPCNET_BATCH_H
 #define LPCNET_BATCH_H
@@ -18,6 +20,7 @@
 #include "lpcnet_engine.h"
 #include "lpcnet_mi355x.h"
 #include "model_host.h"
+#include "side_tables.h"
 
 /* LPCNetBatch is the C API's type, outside the namespace its fields come from */
 using namespace lpcnet_mi355x;
@@ -159,6 +162,33 @@ using PreSync = std::function<int()>;
 void host_reset_state(StreamState &s);
 void reset_signal(StreamState &s);
 bool snapshot_ok(const void *buf);
+/* every value in [-2, 2] or NaN: what a GRU recurrence of this engine leaves */
+bool gru_state_plausible(const float *v, size_t n);
+
+/* Timed regions (lpcnet_batch_kernel_ms; engine.cpp).  mark: with `on`, take
+ * an event and record it on `s` (e = nullptr otherwise).  timed: the pair
+ * (e0, e1) covers `frames` frames of region `which` (0 sample kernel, 1 frame
+ * kernel, 2 PLC predictor, 3 feature extractor); a null event: no pair. */
+int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e);
+void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames);
+
+/* One launch on b->stream as a timed region: with `on`, an event before and
+ * one after it; with timing off no event is taken and nothing but the launch
+ * is queued.  launch() != 0: -1 with `fail` as the error (null: launch has
+ * set its own). */
+template <class Launch>
+int timed_launch(LPCNetBatch *b, int which, bool on, int frames, const char *fail, Launch &&launch)
+{
+  hipEvent_t e0, e1;
+  if (mark(b, on, b->stream, e0)) return -1;
+  if (launch()) {
+    if (fail) set_err(fail);
+    return -1;
+  }
+  if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
+  timed(b, which, e0, e1, frames);
+  return 0;
+}
 
 /* One step for the first nB streams of a batch, host I/O, `pre` queued
  * behind its kernels (engine.cpp, at each definition).  staged: the caller
@@ -168,6 +198,14 @@ int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm, int N
 int tail_first(LPCNetBatch *b, int nB, short *pcm, int N, int preload, const PreSync &pre = PreSync());
 int frame_first(LPCNetBatch *b, int nB, const float *features, bool keep_cond, const PreSync &pre = PreSync());
 int decode_first(LPCNetBatch *b, int nB, const unsigned char *packets, short *pcm, const PreSync &pre = PreSync());
+
+/* side_calls.cpp.  plc_load: after a successful model load, with its blob's
+ * records (optional: a blob without them loads as ever, plc_why says why the
+ * PLC calls refuse it); plc_free, feat_free: the PLC tables and state, the
+ * feature extractor's buffers. */
+void plc_load(LPCNetBatch *b, const std::vector<Arr> &L);
+void plc_free(LPCNetBatch *b);
+void feat_free(LPCNetBatch *b);
 
 }  // namespace lpcnet_mi355x
 

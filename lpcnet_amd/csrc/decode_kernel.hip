@@ -19,7 +19,7 @@
  * Arithmetic: every float expression is the reference's, in its order,
  * compiled with -ffp-contract=off.  pow(2, main_pitch/21.) (double, glibc)
  * is the one transcendental; its 64 possible values come from the host
- * (engine.cpp), computed with the reference's own expression.
+ * (model_host.cpp), computed with the reference's own expression.
  */
 #include "lpcnet_engine.h"
 

@@ -2,7 +2,11 @@
  * engine.cpp -- host side of the MI355X LPCNet synthesis engine and the
  * batch entry points (lpcnet_batch_*, model checks) declared in
  * include/lpcnet_mi355x.h.  The drop-in single-stream API of include/lpcnet.h
- * is dropin.cpp, over the partial-batch steps declared in batch.h.
+ * is dropin.cpp, over the partial-batch steps declared in batch.h.  The calls
+ * beside synthesis -- the PLC predictor, the feature extractor and
+ * lpcnet_mi355x_device_lpc -- are side_calls.cpp, their host-built tables
+ * side_tables.cpp (host-only); this file loads and frees the PLC tables with
+ * the model (plc_load, plc_free) and lends them its timed regions (batch.h).
  *
  * Responsibilities
  *  - upload of a parsed, validated and re-tiled weight blob (model_host.cpp:
@@ -18,13 +22,11 @@
  * Compile with -ffp-contract=off, as every translation unit.
  */
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstddef>
 #include <chrono>
 #include <functional>
@@ -69,75 +71,6 @@ struct Kiss {
     if (jsr == 0) jsr++;
   }
 };
-
-/* ---- lpc_from_cepstrum tables (lpc_kernel.hip) ------------------------- */
-/* The reference's constants, built as the reference builds them: the idct
- * matrix (freq.c:56-59 dct_table), the 320-point kiss FFT twiddles
- * (lpcnet_tables.c kfft, generated by dump_lpcnet_tables.c:88-95 as
- * (float)cos/sin of -2*pi*i/320 in double), kiss_fft's input permutation for
- * factors (4,4,4,5) applied outermost-5-first, and per spectrum bin the band
- * and (float)j/band_size interpolation fraction (freq.c:202-216). */
-void build_lpc_tables(LpcTables &T)
-{
-  static const short eband[LPC_NBANDS] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};
-  static const float comp[LPC_NBANDS] = {0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.666667f, 0.5f, 0.5f, 0.5f,
-                                         0.333333f, 0.25f, 0.25f, 0.2f, 0.166667f, 0.173913f};
-  memset(&T, 0, sizeof(T));
-  const double pi = 3.14159265358979323846264338327;
-  for (int i = 0; i < LPC_WIN; i++) {
-    const double ph = (-2 * pi / LPC_WIN) * i;
-    T.twr[i] = (float)cos(ph);
-    T.twi[i] = (float)sin(ph);
-  }
-  /* per spectrum bin k < 160: band and (float)j/band_size (freq.c:206-213) */
-  unsigned char band[160];
-  float frac[160];
-  for (int b = 0; b < LPC_NBANDS - 1; b++) {
-    const int n = (eband[b + 1] - eband[b]) * 4;
-    for (int j = 0; j < n; j++) {
-      band[eband[b] * 4 + j] = (unsigned char)b;
-      frac[eband[b] * 4 + j] = (float)j / n;
-    }
-  }
-  /* input sample d0 + 5*d1 + 20*d2 + 80*d3 feeds FFT slot d0*64 + d1*16 + d2*4 + d3 */
-  for (int d0 = 0; d0 < 5; d0++)
-    for (int d1 = 0; d1 < 4; d1++)
-      for (int d2 = 0; d2 < 4; d2++)
-        for (int d3 = 0; d3 < 4; d3++) {
-          const int i = d0 * 64 + d1 * 16 + d2 * 4 + d3, bin = d0 + 5 * d1 + 20 * d2 + 80 * d3;
-          const int k = bin <= 160 ? bin : LPC_WIN - bin;
-          LpcSlot &sl = T.slot[i];
-          sl.band = k < 160 ? band[k] : (unsigned char)(LPC_NBANDS - 1);
-          sl.frac = k < 160 ? frac[k] : 0.f;
-          sl.conj = bin > 160 ? 1 : 0;
-        }
-  for (int i = 0; i < LPC_NBANDS; i++)
-    for (int j = 0; j < LPC_NBANDS; j++) {
-      float v = (float)cos((i + .5) * j * M_PI / LPC_NBANDS);
-      if (j == 0) v = (float)(v * sqrt(.5));
-      T.dct[i * LPC_NBANDS + j] = v;
-    }
-  for (int i = 0; i < LPC_NBANDS; i++) T.comp[i] = comp[i];
-  T.sqrt_2_18 = sqrt(2. / LPC_NBANDS);
-  T.scale = 1.f / 320.f;
-}
-
-/* ---- feature extractor tables (feat_kernel.hip) --------------------------- */
-/* half_window as dump_lpcnet_tables.c:83-84 computes it (double, rounded to
- * float; lpcnet_tables.c prints it with nine digits, which round-trip), and
- * lpcn_compute_band_energy's (float)j/band_size of every bin (freq.c:138-141). */
-void build_feat_tables(FeatTables &T)
-{
-  static const short eband[LPC_NBANDS] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};
-  memset(&T, 0, sizeof(T));
-  for (int i = 0; i < FRAME; i++)
-    T.half_window[i] = (float)sin(.5 * M_PI * sin(.5 * M_PI * (i + .5) / FRAME) * sin(.5 * M_PI * (i + .5) / FRAME));
-  for (int b = 0; b < LPC_NBANDS; b++) T.band_start[b] = eband[b] * 4;
-  for (int b = 0; b < LPC_NBANDS - 1; b++) {
-    const int n = (eband[b + 1] - eband[b]) * 4;
-    for (int j = 0; j < n; j++) T.frac[eband[b] * 4 + j] = (float)j / n;
-  }
-}
 
 }  // namespace
 
@@ -329,192 +262,6 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, HostModel &ho
   return 0;
 }
 
-/* ---- PLC prediction network (plc_kernel.hip) ---------------------------- */
-/* The records of training_tf2/dump_plc.py:121-250 under the rules of
- * dense_init, gru_init and find_idx_check (parse_lpcnet_weights.c:90-171);
- * the dimensions the generated plc_data.h would carry come from the record
- * sizes.  Optional in a blob: -1 (set_err names the reason) means the PLC
- * calls refuse the model, never that synthesis does. */
-struct PlcHost {
-  int cond = 0, n[2] = {0, 0};
-  const float *d1_w = nullptr, *d1_b = nullptr, *out_w = nullptr, *out_b = nullptr;
-  std::vector<uint4> g_in[2], g_rec[2];
-  std::vector<int> seed[2];
-};
-
-/* _mm256_cvtps_epi32 on the host: round to nearest even, out of range / NaN -> INT_MIN */
-int host_cvt_rne(float v)
-{
-  if (!(v >= -2147483648.f && v < 2147483648.f)) return INT32_MIN;
-  return (int)nearbyintf(v);
-}
-
-bool plc_dim_ok(int d) { return d >= 64 && d <= PLC_DIM_MAX && d % 64 == 0; }
-
-int plc_parse(const std::vector<Arr> &L, int variant, PlcHost &P, bool tables)
-{
-  static const char *const names[] = {"plc_dense1_weights", "plc_dense1_bias", "plc_gru1_weights", "plc_gru1_weights_idx",
-                                      "plc_gru1_recurrent_weights", "plc_gru1_bias", "plc_gru1_subias", "plc_gru2_weights",
-                                      "plc_gru2_weights_idx", "plc_gru2_recurrent_weights", "plc_gru2_bias",
-                                      "plc_gru2_subias", "plc_out_weights", "plc_out_bias"};
-  bool any = false;
-  for (const char *nm : names) any |= find(L, nm) != nullptr;
-  if (!any) { set_err("PLC: the model blob carries no PLC records (plc_dense1_*, plc_gru1_*, plc_gru2_*, plc_out_*)"); return -1; }
-  for (const char *nm : names)
-    if (!find(L, nm)) { set_err(std::string("PLC: record missing: ") + nm); return -1; }
-  if (variant != LPCNET_VARIANT_INT8) {
-    set_err("PLC: the predictor runs the int8 (DOT_PROD) numerics only; this is an fp32 blob");
-    return -1;
-  }
-  auto sized = [&](const std::string &nm, int bytes) -> const void * {
-    const Arr *a = find(L, nm.c_str());
-    if (!a || a->size != bytes) { set_err("PLC: record mis-sized: " + nm); return nullptr; }
-    return a->data;
-  };
-  const Arr *d1b = find(L, "plc_dense1_bias");
-  if (d1b->size % 4 || !plc_dim_ok(d1b->size / 4)) {
-    set_err("PLC: unsupported plc_dense1 size (a multiple of 64 up to " + std::to_string(PLC_DIM_MAX) + " units)");
-    return -1;
-  }
-  P.cond = d1b->size / 4;
-  P.d1_b = (const float *)d1b->data;
-  /* 57 = 2 NB_BANDS + NB_FEATURES + 1 inputs (lpcnet_plc.c:149) */
-  if (!(P.d1_w = (const float *)sized("plc_dense1_weights", PLC_IN * P.cond * 4))) return -1;
-  int nin = P.cond;
-  for (int k = 0; k < 2; k++) {
-    const std::string nm = k ? "plc_gru2" : "plc_gru1";
-    const Arr *bias = find(L, (nm + "_bias").c_str());
-    if (bias->size % 24 || !plc_dim_ok(bias->size / 24)) {
-      set_err("PLC: unsupported " + nm + " size (a multiple of 64 up to " + std::to_string(PLC_DIM_MAX) + " units)");
-      return -1;
-    }
-    const int n = P.n[k] = bias->size / 24;
-    const float *subias = (const float *)sized(nm + "_subias", 24 * n);
-    if (!subias) return -1;
-    std::vector<std::vector<int>> blocks;
-    if (!parse_idx(L, (nm + "_weights_idx").c_str(), nin, 3 * n, blocks)) { /* gru2: inputs = units1 */
-      set_err("PLC: " + last_err());
-      return -1;
-    }
-    const int8_t *w = (const int8_t *)sized(nm + "_weights", 32 * total_blocks(blocks));
-    const int8_t *rec = (const int8_t *)sized(nm + "_recurrent_weights", 3 * n * n);
-    if (!w || !rec) return -1;
-    for (int b = 0; b < total_blocks(blocks); b++)
-      if (block_may_saturate(w + 32 * b)) { set_err("PLC: " + nm + "_weights: an int8 pair can saturate maddubs (unsupported)"); return -1; }
-    for (int b = 0; b < 3 * n * n / 32; b++)
-      if (block_may_saturate(rec + 32 * b)) {
-        set_err("PLC: " + nm + "_recurrent_weights: an int8 pair can saturate maddubs (unsupported)");
-        return -1;
-      }
-    /* dense [3 n][nin] form of the block-sparse input weights: blocks the idx
-     * leaves out are zero weights, exact in the integer domain (a position
-     * listed twice adds up, as the reference's loop does) */
-    std::vector<int> wi((size_t)3 * n * nin, 0);
-    const int8_t *wp = w;
-    for (size_t rb = 0; rb < blocks.size(); rb++)
-      for (int pos : blocks[rb]) {
-        for (int r = 0; r < 8; r++)
-          for (int c = 0; c < 4; c++) wi[(rb * 8 + r) * nin + pos + c] += wp[r * 4 + c];
-        wp += 32;
-      }
-    for (int v : wi)
-      if (v < -128 || v > 127) { set_err("PLC: " + nm + "_weights_idx lists a block position twice beyond the int8 range"); return -1; }
-    if (tables) {
-      std::vector<int> wr((size_t)3 * n * n);
-      for (int ob = 0; ob < 3 * n / 8; ob++)
-        for (int ib = 0; ib < n / 4; ib++)
-          for (int r = 0; r < 8; r++)
-            for (int c = 0; c < 4; c++) wr[(size_t)(ob * 8 + r) * n + ib * 4 + c] = rec[((size_t)ob * (n / 4) + ib) * 32 + r * 4 + c];
-      /* A tiles of v_mfma_i32_16x16x64_i8 (lpcnet_engine.h PlcArgs) and the seeds */
-      auto tile = [&](const std::vector<int> &W, int K, std::vector<uint4> &out) {
-        const int nk = K / 64;
-        out.resize((size_t)(n / 16) * 3 * nk * 64);
-        for (int ut = 0; ut < n / 16; ut++)
-          for (int g = 0; g < 3; g++)
-            for (int kt = 0; kt < nk; kt++)
-              for (int l = 0; l < 64; l++) {
-                int8_t by[16];
-                const int row = g * n + 16 * ut + l % 16, k0 = 64 * kt + 16 * (l / 16);
-                for (int j = 0; j < 16; j++) by[j] = (int8_t)W[(size_t)row * K + k0 + j];
-                memcpy(&out[(((size_t)ut * 3 + g) * nk + kt) * 64 + l], by, 16);
-              }
-      };
-      tile(wi, nin, P.g_in[k]);
-      tile(wr, n, P.g_rec[k]);
-      P.seed[k].resize(6 * n);
-      const float scale = 128.f * 127.f; /* vec_avx.h:686 */
-      for (int row = 0; row < 3 * n; row++) {
-        int si = 0, sr = 0;
-        for (int j = 0; j < nin; j++) si += wi[(size_t)row * nin + j];
-        for (int j = 0; j < n; j++) sr += wr[(size_t)row * n + j];
-        P.seed[k][row] = (int)((uint32_t)host_cvt_rne(subias[row] * scale) + (uint32_t)(128 * si));
-        P.seed[k][3 * n + row] = (int)((uint32_t)host_cvt_rne(subias[3 * n + row] * scale) + (uint32_t)(128 * sr));
-      }
-    }
-    nin = n;
-  }
-  if (!(P.out_b = (const float *)sized("plc_out_bias", NF * 4))) return -1;
-  if (!(P.out_w = (const float *)sized("plc_out_weights", P.n[1] * NF * 4))) return -1;
-  return 0;
-}
-
-void plc_free(LPCNetBatch *b)
-{
-  for (void *p : b->plc_bufs) (void)hipFree(p);
-  b->plc_bufs.clear();
-  b->d_plc_state = b->d_plc_in = b->d_plc_out = nullptr;
-  b->d_plc_act = nullptr;
-  b->plc_ok = false;
-  b->pa = PlcArgs{};
-}
-
-/* after a successful load_model, with its blob's records: the PLC tables and
- * the per-stream predictor state (zero, as lpcnet_plc_init leaves plc_net) */
-void plc_load(LPCNetBatch *b, const std::vector<Arr> &L)
-{
-  plc_free(b);
-  PlcHost P;
-  if (plc_parse(L, b->variant, P, true)) {
-    b->plc_why = last_err();
-    return;
-  }
-  PlcArgs a{};
-  a.nstreams = b->B;
-  a.cond = P.cond;
-  a.n1 = P.n[0];
-  a.n2 = P.n[1];
-  bool ok = true;
-  auto up = [&](const void *src, size_t bytes) -> void * {
-    void *p = nullptr;
-    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
-    b->plc_bufs.push_back(p);
-    if (src ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(p, 0, bytes) != hipSuccess) ok = false;
-    return p;
-  };
-  a.d1_w = (const float *)up(P.d1_w, (size_t)PLC_IN * P.cond * 4);
-  a.d1_b = (const float *)up(P.d1_b, (size_t)P.cond * 4);
-  a.g1_in = (const uint4 *)up(P.g_in[0].data(), P.g_in[0].size() * sizeof(uint4));
-  a.g1_rec = (const uint4 *)up(P.g_rec[0].data(), P.g_rec[0].size() * sizeof(uint4));
-  a.g1_seed = (const int *)up(P.seed[0].data(), P.seed[0].size() * 4);
-  a.g2_in = (const uint4 *)up(P.g_in[1].data(), P.g_in[1].size() * sizeof(uint4));
-  a.g2_rec = (const uint4 *)up(P.g_rec[1].data(), P.g_rec[1].size() * sizeof(uint4));
-  a.g2_seed = (const int *)up(P.seed[1].data(), P.seed[1].size() * 4);
-  a.out_w = (const float *)up(P.out_w, (size_t)P.n[1] * NF * 4);
-  a.out_b = (const float *)up(P.out_b, NF * 4);
-  a.state = b->d_plc_state = (float *)up(nullptr, (size_t)b->B * (a.n1 + a.n2) * 4);
-  b->d_plc_in = (float *)up(nullptr, (size_t)b->B * PLC_IN * 4);
-  b->d_plc_out = (float *)up(nullptr, (size_t)b->B * NF * 4);
-  b->d_plc_act = (unsigned char *)up(nullptr, (size_t)b->B);
-  if (!ok) {
-    plc_free(b);
-    b->plc_why = "PLC: device allocation or upload of the predictor tables failed";
-    return;
-  }
-  b->pa = a;
-  b->plc_ok = true;
-  b->plc_why.clear();
-}
-
 int ensure_trace(LPCNetBatch *b, int N)
 {
   if (!b->trace) {
@@ -532,13 +279,15 @@ int ensure_trace(LPCNetBatch *b, int N)
   return 0;
 }
 
-/* ---- timed regions (lpcnet_batch_kernel_ms) ------------------------------ */
+}  // namespace
+
+/* ---- timed regions (lpcnet_batch_kernel_ms; batch.h) ---------------------- */
 /* mark: with `on`, take an event and record it on `s` (e = nullptr
  * otherwise: with timing off there are no events at all).  The event belongs
  * to ev_taken from the moment it is taken, so a failing call leaks nothing.
  * timed: the pair (e0, e1) covers `frames` frames of region `which` (0 sample
  * kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor). */
-int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e)
+int lpcnet_mi355x::mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e)
 {
   e = nullptr;
   if (!on) return 0;
@@ -549,13 +298,15 @@ int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e)
   return 0;
 }
 
-void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames)
+void lpcnet_mi355x::timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames)
 {
   if (!e0 || !e1) return;
   b->ev_pairs[which].push_back(e0);
   b->ev_pairs[which].push_back(e1);
   b->ev_frames[which].push_back(frames);
 }
+
+namespace {
 
 /* ---- the sample kernel of a launch ---------------------------------------- */
 /* What every sample launch takes from the batch: N samples for its first nB
@@ -696,12 +447,7 @@ int launch_chunk_samples(LPCNetBatch *b, int f, short *d_pcm, int N, int nfr = 1
   sa.nframes = nfr;
   sa.pcm = d_pcm;
   sa.stamps = b->d_stamps;
-  hipEvent_t e0, e1;
-  if (mark(b, b->timing >= 1, b->stream, e0)) return -1;
-  if (launch_sample_kernel(b, sa)) return -1;
-  if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
-  timed(b, 0, e0, e1, nfr);
-  return 0;
+  return timed_launch(b, 0, b->timing >= 1, nfr, nullptr, [&] { return launch_sample_kernel(b, sa); });
 }
 
 /* Chunked form: the frame network of n frames (features [n][B][NF], their
@@ -717,14 +463,7 @@ int launch_chunk_frames(LPCNetBatch *b, const float *d_features, int n)
   fa.nframes = n;
   fa.cond = b->d_chunk;
   fa.stamps = nullptr;
-  hipEvent_t e0, e1;
-  if (mark(b, b->timing >= 2, b->stream, e0)) return -1;
-  if (launch_chunk(fa, b->stream)) {
-    set_err("chunk kernel launch failed");
-    return -1;
-  }
-  if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
-  timed(b, 1, e0, e1, n);
+  if (timed_launch(b, 1, b->timing >= 2, n, "chunk kernel launch failed", [&] { return launch_chunk(fa, b->stream); })) return -1;
   b->frames_done(n);
   return 0;
 }
@@ -772,21 +511,23 @@ void reset_signal(StreamState &s)
   memset(s.gru_b_state, 0, sizeof(s.gru_b_state));
 }
 
+/* GRU states are convex combinations of earlier states and tanh outputs:
+ * |x| <= 1 (+ rounding) or NaN for every state the recurrence produces.
+ * The int8 kernels' state quantiser relies on |x| < 2^24 (quant_s8_state),
+ * so a snapshot outside that range is not one of ours: its restore refuses it. */
+bool gru_state_plausible(const float *v, size_t n)
+{
+  for (size_t k = 0; k < n; k++)
+    if (v[k] > 2.f || v[k] < -2.f) return false;
+  return true;
+}
+
 /* A snapshot is restored only if it is one this engine can have produced. */
 bool snapshot_ok(const void *buf)
 {
-  /* GRU states are convex combinations of earlier states and tanh outputs:
-   * |x| <= 1 (+ rounding) or NaN for every state the recurrence produces.
-   * The int8 kernels' state quantiser relies on |x| < 2^24 (quant_s8_state),
-   * so a snapshot outside that range is not one of ours: refuse it. */
   StreamState tmp;
   memcpy(&tmp, buf, sizeof(tmp));
-  auto bad = [](const float *v, int n) {
-    for (int k = 0; k < n; k++)
-      if (v[k] > 2.f || v[k] < -2.f) return true;
-    return false;
-  };
-  if (bad(tmp.gru_a_state, NA) || bad(tmp.gru_b_state, NB)) {
+  if (!gru_state_plausible(tmp.gru_a_state, NA) || !gru_state_plausible(tmp.gru_b_state, NB)) {
     set_err("snapshot GRU state outside [-2, 2]: not a state this engine produced");
     return false;
   }
@@ -852,32 +593,6 @@ LPCNET_EXPORT int lpcnet_mi355x_device_count(void)
 
 LPCNET_EXPORT const uint32_t *lpcnet_mi355x_rcp_table(void) { return kRcpTable; }
 
-LPCNET_EXPORT int lpcnet_mi355x_device_lpc(int device, const float *cepstra, float *lpc, int n)
-{
-  if (n < 0 || (n > 0 && (!cepstra || !lpc))) { set_err("bad arguments"); return -1; }
-  if (n == 0) return 0;
-  if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice failed"); return -1; }
-  LpcTables T;
-  build_lpc_tables(T);
-  float *dc = nullptr, *dl = nullptr;
-  LpcTables *dt = nullptr;
-  int rc = -1;
-  if (hipMalloc(&dc, sizeof(float) * NF * (size_t)n) == hipSuccess && hipMalloc(&dl, sizeof(float) * NLPC * (size_t)n) == hipSuccess &&
-      hipMalloc(&dt, sizeof(T)) == hipSuccess && hipMemcpy(dt, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess) {
-    /* cepstra arrive as [n][NLPC+2] (18 bands); the kernel reads [n][NF] */
-    std::vector<float> f((size_t)NF * n, 0.f);
-    for (int i = 0; i < n; i++) memcpy(&f[(size_t)i * NF], cepstra + (size_t)i * LPC_NBANDS, sizeof(float) * LPC_NBANDS);
-    if (hipMemcpy(dc, f.data(), f.size() * 4, hipMemcpyHostToDevice) == hipSuccess && launch_lpc(dc, dl, n, dt, nullptr) == 0 &&
-        hipMemcpy(lpc, dl, sizeof(float) * NLPC * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess)
-      rc = 0;
-  }
-  if (rc) set_err("device LPC failed");
-  (void)hipFree(dc);
-  (void)hipFree(dl);
-  (void)hipFree(dt);
-  return rc;
-}
-
 LPCNET_EXPORT LPCNetBatch *lpcnet_batch_create(int nb_streams, int device)
 {
   if (nb_streams < 1) { set_err("nb_streams < 1"); return nullptr; }
@@ -932,11 +647,7 @@ LPCNET_EXPORT void lpcnet_batch_destroy(LPCNetBatch *b)
   if (b->fstream) (void)hipStreamSynchronize(b->fstream);
   free_model(b);
   plc_free(b);
-  (void)hipFree(b->d_feat_state);
-  (void)hipFree(b->d_feat_tab);
-  (void)hipFree(b->d_feat_pcm);
-  (void)hipFree(b->d_feat_out);
-  (void)hipFree(b->d_feat_act);
+  feat_free(b);
   (void)hipFree(b->d_state);
   (void)hipFree(b->d_ck_sync);
   (void)hipFree(b->d_feat);
@@ -1702,275 +1413,6 @@ LPCNET_EXPORT int lpcnet_batch_get_state(LPCNetBatch *b, int stream, float *gru_
   if (gru_a_state) memcpy(gru_a_state, s.gru_a_state, sizeof(s.gru_a_state));
   if (gru_b_state) memcpy(gru_b_state, s.gru_b_state, sizeof(s.gru_b_state));
   if (frame_count) *frame_count = s.frame_count;
-  return 0;
-}
-
-/* ---- PLC prediction network ---------------------------------------------- */
-
-static int plc_ready(const LPCNetBatch *b)
-{
-  if (!b) { set_err("null batch"); return -1; }
-  if (!b->have_model) { set_err("no model loaded"); return -1; }
-  if (!b->plc_ok) { set_err(b->plc_why.empty() ? "PLC: no usable PLC records" : b->plc_why); return -1; }
-  return 0;
-}
-
-/* one predictor launch on the batch's stream (timed as which = 2 when timing is on) */
-static int plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
-{
-  PlcArgs a = b->pa;
-  a.in = d_in;
-  a.out = d_out;
-  a.active = d_active;
-  a.rcp = b->fa.rcp;
-  a.rcp_hw = b->sa.rcp_hw;
-  hipEvent_t e0, e1;
-  if (mark(b, b->timing != 0, b->stream, e0)) return -1;
-  if (launch_plc(a, b->stream)) { set_err("plc kernel launch failed"); return -1; }
-  if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
-  timed(b, 2, e0, e1, 1);
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_mi355x_plc_dims(const unsigned char *data, int len, int dims[4])
-{
-  std::vector<Arr> L;
-  if (!data || len <= 0 || !dims || !parse_blob(L, data, len)) { set_err("malformed weight blob"); return -1; }
-  GruASparse A; /* the blob's variant as a load chooses it */
-  if (parse_gru_a(L, A)) {
-    /* this call's own wording for a blob without the weight record */
-    if (last_err() == "missing sparse_gru_a_recurrent_weights")
-      set_err("sparse_gru_a_recurrent_weights size matches neither int8 nor fp32");
-    return -1;
-  }
-  PlcHost P;
-  if (plc_parse(L, A.variant, P, false)) return -1;
-  dims[0] = PLC_IN;
-  dims[1] = P.cond;
-  dims[2] = P.n[0];
-  dims[3] = P.n[1];
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_info(const LPCNetBatch *b, int dims[4])
-{
-  if (plc_ready(b)) return -1;
-  if (!dims) { set_err("bad arguments"); return -1; }
-  dims[0] = PLC_IN;
-  dims[1] = b->pa.cond;
-  dims[2] = b->pa.n1;
-  dims[3] = b->pa.n2;
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_predict_device(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
-{
-  if (plc_ready(b) || b->set_device()) return -1;
-  return plc_launch(b, d_in, d_out, d_active);
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_predict(LPCNetBatch *b, const float *in, float *out, const unsigned char *active)
-{
-  if (plc_ready(b) || b->set_device()) return -1;
-  const size_t B = (size_t)b->B;
-  if (in) HIPCHK(hipMemcpyAsync(b->d_plc_in, in, B * PLC_IN * 4, hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_plc_act, active, B, hipMemcpyHostToDevice, b->stream));
-  if (plc_launch(b, in ? b->d_plc_in : nullptr, out ? b->d_plc_out : nullptr, active ? b->d_plc_act : nullptr)) return -1;
-  if (!out) {
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return 0;
-  }
-  /* inactive streams keep their out row: the staging rows of the active ones only */
-  std::vector<float> tmp(B * NF);
-  HIPCHK(hipMemcpyAsync(tmp.data(), b->d_plc_out, tmp.size() * 4, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  for (size_t s = 0; s < B; s++)
-    if (!active || active[s]) memcpy(out + s * NF, &tmp[s * NF], NF * 4);
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int stream)
-{
-  if (plc_ready(b) || b->set_device()) return -1;
-  if (stream < -1 || stream >= b->B) { set_err("no such stream"); return -1; }
-  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-  if (stream < 0) HIPCHK(hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * nt * 4, b->stream));
-  else HIPCHK(hipMemsetAsync(b->d_plc_state + (size_t)stream * nt, 0, nt * 4, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_state_size(const LPCNetBatch *b)
-{
-  if (plc_ready(b)) return -1;
-  return (b->pa.n1 + b->pa.n2) * 4;
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_save_state(LPCNetBatch *b, int stream, void *buf)
-{
-  if (plc_ready(b) || b->set_device()) return -1;
-  if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
-  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, b->d_plc_state + (size_t)stream * nt, nt * 4, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, const void *buf)
-{
-  if (plc_ready(b) || b->set_device()) return -1;
-  if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
-  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-  /* as snapshot_ok: a GRU state this engine produced lies in [-1, 1] (+ rounding) or is NaN */
-  std::vector<float> v(nt);
-  memcpy(v.data(), buf, nt * 4);
-  for (float x : v)
-    if (x > 2.f || x < -2.f) { set_err("PLC snapshot GRU state outside [-2, 2]: not a state this engine produced"); return -1; }
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(b->d_plc_state + (size_t)stream * nt, buf, nt * 4, hipMemcpyHostToDevice));
-  return 0;
-}
-
-/* ---- feature extractor (lpcnet_compute_single_frame_features) ------------- */
-
-/* the analysis state, tables and staging of a batch, on its first extraction */
-static int feat_ensure(LPCNetBatch *b)
-{
-  if (b->d_feat_state) return 0;
-  const size_t B = (size_t)b->B;
-  FeatTables T;
-  build_feat_tables(T);
-  FeatState *st = nullptr;
-  FeatTables *tab = nullptr;
-  float *pcm = nullptr, *out = nullptr;
-  unsigned char *act = nullptr;
-  const bool ok = hipMalloc(&st, sizeof(FeatState) * B) == hipSuccess &&
-                  hipMemsetAsync(st, 0, sizeof(FeatState) * B, b->stream) == hipSuccess && /* ordered before the first launch */
-                  hipMalloc(&tab, sizeof(T)) == hipSuccess && hipMemcpy(tab, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMalloc(&pcm, B * FRAME * 4) == hipSuccess && hipMalloc(&out, B * NTF * 4) == hipSuccess &&
-                  hipMalloc(&act, B) == hipSuccess;
-  if (!ok) {
-    (void)hipFree(st);
-    (void)hipFree(tab);
-    (void)hipFree(pcm);
-    (void)hipFree(out);
-    (void)hipFree(act);
-    set_err("features: device allocation failed");
-    return -1;
-  }
-  b->d_feat_state = st;
-  b->d_feat_tab = tab;
-  b->d_feat_pcm = pcm;
-  b->d_feat_out = out;
-  b->d_feat_act = act;
-  return 0;
-}
-
-/* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
-static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
-                       const unsigned char *d_active)
-{
-  FeatArgs a{};
-  a.nstreams = b->B;
-  a.pcm = d_pcm;
-  a.pcm_f = d_pcm_f;
-  a.features = d_features;
-  a.row = row;
-  a.active = d_active;
-  a.state = b->d_feat_state;
-  a.lpc_tab = b->d_lpc_tab;
-  a.tab = b->d_feat_tab;
-  hipEvent_t e0, e1;
-  if (mark(b, b->timing != 0, b->stream, e0)) return -1;
-  if (launch_feat(a, b->stream)) { set_err("feature kernel launch failed"); return -1; }
-  if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
-  timed(b, 3, e0, e1, 1);
-  return 0;
-}
-
-static int feat_host(LPCNetBatch *b, const void *pcm, bool is_float, float *features, const unsigned char *active)
-{
-  if (!pcm || !features) { set_err("bad arguments"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (b->set_device() || feat_ensure(b)) return -1;
-  const size_t B = (size_t)b->B;
-  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * (is_float ? 4 : 2), hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
-  if (feat_launch(b, is_float ? nullptr : (const short *)b->d_feat_pcm, is_float ? b->d_feat_pcm : nullptr, b->d_feat_out, NTF,
-                  active ? b->d_feat_act : nullptr))
-    return -1;
-  /* inactive streams keep their row: the staging rows of the active ones only */
-  std::vector<float> tmp(B * NTF);
-  HIPCHK(hipMemcpyAsync(tmp.data(), b->d_feat_out, tmp.size() * 4, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  for (size_t s = 0; s < B; s++)
-    if (!active || active[s]) memcpy(features + s * NTF, &tmp[s * NTF], NTF * 4);
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_compute_features(LPCNetBatch *b, const short *pcm, float *features, const unsigned char *active)
-{
-  return feat_host(b, pcm, false, features, active);
-}
-
-LPCNET_EXPORT int lpcnet_batch_compute_features_float(LPCNetBatch *b, const float *pcm, float *features,
-                                                      const unsigned char *active)
-{
-  return feat_host(b, pcm, true, features, active);
-}
-
-LPCNET_EXPORT int lpcnet_batch_compute_features_device(LPCNetBatch *b, const short *d_pcm, float *d_features, int row,
-                                                       const unsigned char *d_active, int nframes)
-{
-  if (row != NF && row != NTF) { set_err("features: row must be NB_FEATURES (20) or NB_TOTAL_FEATURES (36)"); return -1; }
-  if (nframes < 0) { set_err("features: nframes < 0"); return -1; }
-  if (!d_pcm || !d_features) { set_err("bad arguments"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (b->set_device() || feat_ensure(b)) return -1;
-  /* the frames of a stream are sequential: one launch per frame, in stream order */
-  for (int f = 0; f < nframes; f++)
-    if (feat_launch(b, d_pcm + (size_t)f * b->B * FRAME, nullptr, d_features + (size_t)f * b->B * row, row, d_active)) return -1;
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream)
-{
-  if (stream < -1) { set_err("no such stream"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (!b->d_feat_state) return 0; /* never used: a first use starts from the reset state */
-  if (b->set_device()) return -1;
-  if (stream < 0) HIPCHK(hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream));
-  else HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *) { return (int)sizeof(FeatState); }
-
-LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf)
-{
-  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (b->set_device() || feat_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, b->d_feat_state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf)
-{
-  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
-  /* the kernel indexes its Viterbi rows with best_i */
-  FeatState s;
-  memcpy(&s, buf, sizeof(s));
-  if (s.best_i < 0 || s.best_i >= PITCH_STATES) { set_err("features snapshot: best_i outside [0, 224): not a state this engine produced"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (b->set_device() || feat_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(b->d_feat_state + stream, &s, sizeof(s), hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -380,7 +380,7 @@ int fp_lds_bytes();
 int launch_fp(const SampleArgs &a, void *stream);
 
 /* lpc_from_cepstrum on the device (lpc_kernel.hip).  Constant tables built
- * once per batch on the host (engine.cpp build_lpc_tables): the idct matrix
+ * once per batch on the host (side_tables.cpp build_lpc_tables): the idct matrix
  * (freq.c dct_table), the 320-point kiss FFT twiddles and input permutation
  * (kiss_fft.c, lpcnet_tables.c), the band index and interpolation fraction of
  * every spectrum bin (freq.c:202-216), the compensation factors (freq.c:50). */

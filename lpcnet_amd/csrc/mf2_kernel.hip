@@ -59,7 +59,7 @@ int mf2_lds_bytes(int S, int split)
 }
 
 /* SPLIT: models with block rows beyond the register tables (trained
- * Sparsify masks, engine.cpp mf_plan) -- each lane group also runs a hosted
+ * Sparsify masks, mf_plan.cpp mf_plan) -- each lane group also runs a hosted
  * piece of another row, whose partial sums reach the row's owner through
  * LDS: one buffer per group, added into by the group's recurrent product and
  * merged (then cleared) by its next elementwise step, a barrier apart */

@@ -122,7 +122,7 @@ __device__ __forceinline__ void mf_run(const unsigned char *lds, const uint32_t 
   }
 }
 
-/* Split models (engine.cpp mf_plan): the z and r products over NO own
+/* Split models (mf_plan.cpp mf_plan): the z and r products over NO own
  * groups into az / ar and NF hosted groups (a piece of another row) into
  * fz / fr, compile-time counts (a runtime own/hosted choice per group makes
  * the compiler issue the next group's LDS reads only after the current

@@ -269,7 +269,7 @@ template <int MFW_G, int Z, int H, bool SPLIT = false, bool HOST = false>
 __device__ __forceinline__ void mfw_r_role(const SampleArgs &A, unsigned char *xa, int *trm, int r, int lane, int total,
                                            int *prt = nullptr)
 {
-  /* this lane's weight words and packed column quads (engine.cpp mf tables:
+  /* this lane's weight words and packed column quads (mf_plan.cpp mf tables:
    * z slots 0..15, r 16..31, h 32..63, quads 4 per word after them) */
   uint32_t wz[4 * Z], wr[4 * Z], wh[4 * H], cz[Z], cr[Z], ch[H];
   const uint32_t *mt = (SPLIT ? A.mfw_tab : A.mf) + (size_t)r * MF_LANE_U32 * 64 + lane;

@@ -26,27 +26,36 @@
  * dense GRU_B tiles decode to the blob's GRU_B.  A model the planner
  * declines (the lockstep kernel runs it) is counted, not failed.
  *
+ * For the synthetic PLC predictors (side_tables.cpp plc_parse; the default
+ * shape 128 / 256 / 256 and the small one 64 / 128 / 64) it decodes the input
+ * and recurrent v_mfma_i32_16x16x64_i8 A tiles of both GRUs into dense
+ * [3 n][K] matrices that must equal the ones assembled from the blob's index,
+ * weight and recurrent-weight records, and recomputes every seed from subias
+ * and the decoded rows' sums.
+ *
  * Under AddressSanitizer and UBSan (host code only):
  *
- *   make build_san/mf_plan.o build_san/model_host.o build_san/model_gen.o build_san/host_rcpps.o BUILD=build_san \
- *        EXTRA="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer"
+ *   make build_san/mf_plan.o build_san/model_host.o build_san/side_tables.o build_san/model_gen.o build_san/host_rcpps.o \
+ *        BUILD=build_san EXTRA="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer"
  *   /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Iinclude -Ilpcnet_amd/csrc \
  *        -Xarch_host -fsanitize=address,undefined -c tools/model_host_check.cpp -o build_san/model_host_check.o
  *   /opt/rocm/llvm/bin/clang++ -fsanitize=address,undefined -o build_san/model_host_check build_san/model_host_check.o \
- *        build_san/model_host.o build_san/mf_plan.o build_san/model_gen.o build_san/host_rcpps.o
+ *        build_san/model_host.o build_san/side_tables.o build_san/mf_plan.o build_san/model_gen.o build_san/host_rcpps.o
  *   (the compiler hipcc drives: the objects' sanitizer calls need its runtime)
  *   build_san/model_host_check
  *
  * Exit status 0 and one "model_host_check ok" line when every check holds.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <set>
+#include <string>
 #include <vector>
 
-#include "model_host.h"
+#include "side_tables.h"
 
 using namespace lpcnet_mi355x;
 
@@ -323,6 +332,95 @@ static void check_model(const char *name, const unsigned char *blob, int n, int 
   unsetenv("LPCNET_MF_FORCE_SPLIT");
 }
 
+static int plc_decoded;
+
+/* A tiles [unit tile][gate][k tile][64 lanes] of 16 bytes (lpcnet_engine.h PlcArgs) -> dense [3 n][K] */
+static bool decode_plc_tiles(const std::vector<uint4> &tiles, int n, int K, std::vector<int> &D, const char *what)
+{
+  const int nk = K / 64;
+  D.assign((size_t)3 * n * K, 0);
+  CHECK(tiles.size() == (size_t)(n / 16) * 3 * nk * 64, "%s: %zu tiles for n %d K %d", what, tiles.size(), n, K);
+  if (tiles.size() != (size_t)(n / 16) * 3 * nk * 64) return false;
+  const int8_t *by = (const int8_t *)tiles.data();
+  for (int ut = 0; ut < n / 16; ut++)
+    for (int g = 0; g < 3; g++)
+      for (int kt = 0; kt < nk; kt++)
+        for (int l = 0; l < 64; l++) {
+          const int row = g * n + 16 * ut + l % 16, k0 = 64 * kt + 16 * (l / 16);
+          for (int j = 0; j < 16; j++) D[(size_t)row * K + k0 + j] += by[((((size_t)ut * 3 + g) * nk + kt) * 64 + l) * 16 + j];
+        }
+  return true;
+}
+
+/* The PLC predictor of a synthetic blob: the input and recurrent A tiles of
+ * both GRUs decode to the matrices assembled from the blob's _weights_idx /
+ * _weights / _recurrent_weights records (as check_gru_b assembles GRU_B's),
+ * and every seed is rne(subias * 128 * 127) + 128 * the decoded row's sum. */
+static void check_plc(const char *name, int flags, int cond, int n1, int n2)
+{
+  const int len = lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, flags, nullptr, 0);
+  std::vector<unsigned char> blob(len);
+  lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, flags, blob.data(), len);
+  std::vector<Arr> L;
+  PlcHost P;
+  if (!parse_blob(L, blob.data(), len) || plc_parse(L, LPCNET_VARIANT_INT8, P, true)) {
+    CHECK(false, "%s: PLC records do not parse (%s)", name, last_err().c_str());
+    return;
+  }
+  CHECK(P.cond == cond && P.n[0] == n1 && P.n[1] == n2, "%s: dims %d %d %d", name, P.cond, P.n[0], P.n[1]);
+  int nin = P.cond;
+  for (int k = 0; k < 2; k++) {
+    const int n = P.n[k];
+    const std::string nm = k ? "plc_gru2" : "plc_gru1";
+    char tag[80];
+    snprintf(tag, sizeof tag, "%s/%s", name, nm.c_str());
+    std::vector<std::vector<int>> blocks;
+    const Arr *w = find(L, (nm + "_weights").c_str()), *r = find(L, (nm + "_recurrent_weights").c_str());
+    const Arr *sb = find(L, (nm + "_subias").c_str());
+    if (!parse_idx(L, (nm + "_weights_idx").c_str(), nin, 3 * n, blocks) || !w || !r || !sb || sb->size != 24 * n ||
+        w->size != 32 * total_blocks(blocks) || r->size != 3 * n * n) {
+      CHECK(false, "%s: records", tag);
+      return;
+    }
+    std::vector<int> Rin((size_t)3 * n * nin, 0), Rrec((size_t)3 * n * n, 0), Din, Drec;
+    const int8_t *wb = (const int8_t *)w->data, *wr = (const int8_t *)r->data;
+    int t = 0;
+    for (int rb = 0; rb < 3 * n / 8; rb++)
+      for (int pos : blocks[rb]) {
+        for (int i = 0; i < 8; i++)
+          for (int c = 0; c < 4; c++) Rin[(size_t)(rb * 8 + i) * nin + pos + c] += wb[32 * t + 4 * i + c];
+        t++;
+      }
+    for (int rb = 0; rb < 3 * n / 8; rb++)
+      for (int cb = 0; cb < n / 4; cb++)
+        for (int i = 0; i < 8; i++)
+          for (int c = 0; c < 4; c++) Rrec[(size_t)(rb * 8 + i) * n + 4 * cb + c] = wr[32 * ((size_t)rb * (n / 4) + cb) + 4 * i + c];
+    if (!decode_plc_tiles(P.g_in[k], n, nin, Din, tag) || !decode_plc_tiles(P.g_rec[k], n, n, Drec, tag)) return;
+    CHECK(Din == Rin, "%s: input tiles differ from the blob", tag);
+    CHECK(Drec == Rrec, "%s: recurrent tiles differ from the blob", tag);
+    CHECK(P.seed[k].size() == (size_t)6 * n, "%s: %zu seeds", tag, P.seed[k].size());
+    if (P.seed[k].size() != (size_t)6 * n) return;
+    const float *subias = (const float *)sb->data;
+    for (int half = 0; half < 2; half++) {
+      const std::vector<int> &D = half ? Drec : Din;
+      const int K = half ? n : nin;
+      for (int row = 0; row < 3 * n; row++) {
+        int sum = 0;
+        for (int j = 0; j < K; j++) sum += D[(size_t)row * K + j];
+        /* _mm256_cvtps_epi32: round to nearest even; the synthetic subias stay far inside the int range */
+        const float v = subias[half * 3 * n + row] * (128.f * 127.f);
+        CHECK(fabsf(v) < 2147483648.f, "%s: subias %d of half %d out of range", tag, row, half);
+        if (!(fabsf(v) < 2147483648.f)) continue;
+        const int want = (int)((uint32_t)(int)nearbyintf(v) + (uint32_t)(128 * sum));
+        CHECK(P.seed[k][half * 3 * n + row] == want, "%s: seed %d of half %d is %d, recomputed %d", tag, row, half,
+              P.seed[k][half * 3 * n + row], want);
+      }
+    }
+    nin = n;
+  }
+  plc_decoded++;
+}
+
 static bool read_file(const char *path, std::vector<unsigned char> &out)
 {
   FILE *f = fopen(path, "rb");
@@ -365,12 +463,16 @@ int main(int argc, char **argv)
         snprintf(name, sizeof name, "%s/seed %u", m.name, seed);
         check_model(name, blob.data(), n, seed == 1 ? m.mf : m.mf_other_seeds, false);
       }
+    /* synthetic-model flags 8: PLC records in the default shape, 8 | 16: in the small one */
+    check_plc("plc", 8, 128, 256, 256);
+    check_plc("plc_small", 8 | 16, 64, 128, 64);
   }
   if (fails) {
     fprintf(stderr, "model_host_check: %d checks failed\n", fails);
     return 1;
   }
-  printf("model_host_check ok (%d plans decoded, %d split, %d with the wide split form; %d declined by the planner)\n", plans,
-         split_plans, wide_plans, declined);
+  printf("model_host_check ok (%d plans decoded, %d split, %d with the wide split form; %d declined by the planner; "
+         "%d PLC predictors decoded)\n",
+         plans, split_plans, wide_plans, declined, plc_decoded);
   return 0;
 }
