@@ -307,8 +307,9 @@ __global__ __launch_bounds__(CK_THREADS) void chunk_kernel(FrameArgs A)
       const int s = e / (G::INF * FIN), rem = e % (G::INF * FIN);
       const int fr = rem / FIN - 2, j = rem % FIN, sid = s0 + s;
       if (sid < B && fr >= 0 && fr < n && j >= NF) {
-        /* lpcnet.c:93-94: the 0.1 avoids rounding issues */
-        int pitch = (int)floor(.1 + (double)(50.f * vin[q]) + 100);
+        /* lpcnet.c:93-94: the 0.1 avoids rounding issues; the cast is x86's
+         * (beyond int, +-inf, NaN: INT_MIN, hence row 33) */
+        int pitch = cvtt_f64(floor(.1 + (double)(50.f * vin[q]) + 100));
         pitch = min(255, max(33, pitch));
         vin[q] = A.embed_pitch[pitch * EP + (j - NF)];
       }

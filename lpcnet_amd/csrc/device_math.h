@@ -338,6 +338,14 @@ __device__ __forceinline__ int cvt_rne(float v)
   return r < 2147483648.f ? c : (int)0x80000000u;
 }
 
+/* (int) of a double on x86 (cvttsd2si): truncation, out of range / NaN ->
+ * INT_MIN.  v_cvt_i32_f64 saturates (+big -> INT_MAX) and maps NaN to 0;
+ * a double in (-2^31 - 1, -2^31) truncates to INT_MIN on both. */
+__device__ __forceinline__ int cvtt_f64(double v)
+{
+  return v > -2147483649.0 && v < 2147483648.0 ? (int)v : (int)0x80000000u;
+}
+
 /* vector_ps_to_epi8 (vec_avx.h:321-336) -> u8, returned XOR 0x80 (= u8-128,
  * the signed form the int8 products consume): cvtps_epi32 then two unsigned
  * saturating packs, i.e. 0 for NaN / r >= 2^31 (INT_MIN) and r <= 0,

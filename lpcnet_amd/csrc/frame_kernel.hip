@@ -172,9 +172,10 @@ __global__ __launch_bounds__(FK_THREADS) void frame_kernel(FrameArgs A)
       } else if (j < 2 * FIN + NF) {
         v1[q] = A.features[sid * NF + (j - 2 * FIN)];
       } else {
-        /* lpcnet.c:93-94: the 0.1 avoids rounding issues */
+        /* lpcnet.c:93-94: the 0.1 avoids rounding issues; the cast is x86's
+         * (beyond int, +-inf, NaN: INT_MIN, hence row 33) */
         const float f18 = A.features[sid * NF + 18];
-        int pitch = (int)floor(.1 + (double)(50.f * f18) + 100);
+        int pitch = cvtt_f64(floor(.1 + (double)(50.f * f18) + 100));
         pitch = min(255, max(33, pitch));
         v1[q] = A.embed_pitch[pitch * EP + (j - 2 * FIN - NF)];
       }

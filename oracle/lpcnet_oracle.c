@@ -715,6 +715,12 @@ void oracle_get_state(const OracleState *st, float *a, float *b)
   if (b) memcpy(b, st->gru_b_state, sizeof(st->gru_b_state));
 }
 
+void oracle_get_conv_mem(const OracleState *st, float *c1, float *c2)
+{
+  if (c1) memcpy(c1, st->conv1_mem, sizeof(st->conv1_mem));
+  if (c2) memcpy(c2, st->conv2_mem, sizeof(st->conv2_mem));
+}
+
 /* nnet.c:122-135 _lpcnet_compute_dense (all row counts here are multiples of 16) */
 static void dense(const OracleState *st, float *out, const float *w, const float *b, int nin, int nout, int tanh_act, const float *in)
 {

@@ -117,6 +117,8 @@ void oracle_set_trace(OracleState *st, float *logits8, int *exc, uint32_t *rng_w
 void oracle_get_frame(const OracleState *st, float *gru_a_cond /*1152*/, float *gru_b_cond /*48*/, float *lpc /*16*/);
 int oracle_frame_count(const OracleState *st);
 void oracle_get_state(const OracleState *st, float *gru_a_state /*384*/, float *gru_b_state /*16*/);
+/* The conv memories of run_frame_network (the inputs of the last two frames). */
+void oracle_get_conv_mem(const OracleState *st, float *conv1_mem /*168*/, float *conv2_mem /*256*/);
 
 #ifdef __cplusplus
 }

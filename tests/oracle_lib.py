@@ -39,6 +39,7 @@ _SIGS = [
     ("oracle_get_frame", None, [_vp, _vp, _vp, _vp]),
     ("oracle_frame_count", _i, [_vp]),
     ("oracle_get_state", None, [_vp, _vp, _vp]),
+    ("oracle_get_conv_mem", None, [_vp, _vp, _vp]),
     ("oracle_synthesize_tail", None, [_vp, _vp, _i, _i]),
     ("oracle_frame_deferred", None, [_vp, _vp]),
     ("oracle_frame_flush", None, [_vp]),
@@ -245,6 +246,13 @@ class Oracle:
         b = np.zeros(16, np.float32)
         self._lib.oracle_get_state(self._st, a.ctypes.data, b.ctypes.data)
         return a, b
+
+    def conv_mem(self):
+        """(conv1 memory [168], conv2 memory [256]) of run_frame_network."""
+        c1 = np.zeros(168, np.float32)
+        c2 = np.zeros(256, np.float32)
+        self._lib.oracle_get_conv_mem(self._st, c1.ctypes.data, c2.ctypes.data)
+        return c1, c2
 
     def frame_count(self) -> int:
         return self._lib.oracle_frame_count(self._st)
