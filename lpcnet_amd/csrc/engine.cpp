@@ -152,7 +152,7 @@ LdsSizes lds_sizes(const ModelCaps &c)
   LdsSizes l;
   l.fp = fp_lds_bytes();
   l.mf = mf_lds_bytes(c.S, c.mf_split);
-  l.mf2 = mf2_lds_bytes(4, c.mf_split);
+  l.mf2 = mf2_lds_bytes(c.mf_split);
   l.mfw[0] = mfw_lds_bytes(2, c.mf_split);
   l.mfw[1] = mfw_lds_bytes(3, c.mf_split);
   return l;
@@ -339,7 +339,7 @@ int launch_sample_kernel(LPCNetBatch *b, const SampleArgs &sa)
   switch (launch_kernel(b, sa.nstreams, sa.preload != 0, sa.stamps != nullptr)) {
   case SampleKernel::FP: rc = launch_fp(sa, b->stream); break;
   case SampleKernel::MFW: rc = launch_mfw(sa, b->plan.mfw_g, b->stream); break;
-  case SampleKernel::MF2: rc = launch_mf2(sa, 4, b->stream); break;
+  case SampleKernel::MF2: rc = launch_mf2(sa, b->stream); break;
   case SampleKernel::MF: rc = launch_mf(sa, b->caps.S, mf_lds_bytes(b->caps.S, b->sa.mf_split), b->stream); break;
   case SampleKernel::LOCKSTEP:
     rc = launch_sample(sa, b->caps.S, b->variant, b->sat ? 1 : 0, b->caps.reg ? 1 : 0, b->caps.lds_bytes, b->stream);

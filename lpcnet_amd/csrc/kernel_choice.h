@@ -56,7 +56,7 @@ struct ModelCaps {
 struct LdsSizes {
   int fp = 0;            /* fp_lds_bytes() */
   int mf = 0;            /* mf_lds_bytes(S, mf_split) */
-  int mf2 = 0;           /* mf2_lds_bytes(4, mf_split) */
+  int mf2 = 0;           /* mf2_lds_bytes(mf_split) */
   int mfw[2] = {0, 0};   /* mfw_lds_bytes(2 | 3, mf_split) */
 };
 

@@ -364,8 +364,8 @@ int mf_lds_bytes(int S, int split);
 int launch_mf(const SampleArgs &a, int S, int lds_bytes, void *stream);
 /* Large batches: two groups of S streams per workgroup, half a sample
  * apart (mf2_kernel.hip); no preload / trace / stamps. */
-int mf2_lds_bytes(int S, int split);
-int launch_mf2(const SampleArgs &a, int S, void *stream);
+int mf2_lds_bytes(int split);
+int launch_mf2(const SampleArgs &a, void *stream);
 /* wide-batch kernel (mfw_kernel.hip): 2 or 3 four-stream groups per
  * 896-thread workgroup with dedicated gather/elementwise, recurrent and
  * sampler waves (split models: two groups, 1,024 threads with two host

@@ -1,6 +1,6 @@
 /*
  * mf2_kernel.hip -- the matrix-core sample kernel for large batches: two
- * groups of S streams per 512-thread workgroup, half a sample apart
+ * groups of S = 4 streams per 512-thread workgroup, half a sample apart
  * (lpcnet_synthesize_tail_impl, lpcnet.c:235-271; arithmetic term for term
  * mf_kernel's, which is the reference's).
  *
@@ -52,10 +52,9 @@ struct Mf2Lds {
   static constexpr int part = 2 * 3 * (NA + 1) * S * 4; /* split models: hosted partial sums [group][3][NA + 1][S] */
 };
 
-int mf2_lds_bytes(int S, int split)
+int mf2_lds_bytes(int split)
 {
-  return IMG_VAR + (S == 4 ? Mf2Lds<4>::total + (split ? Mf2Lds<4>::part : 0)
-                           : Mf2Lds<2>::total + (split ? Mf2Lds<2>::part : 0));
+  return IMG_VAR + Mf2Lds<4>::total + (split ? Mf2Lds<4>::part : 0);
 }
 
 /* SPLIT: models with block rows beyond the register tables (trained
@@ -66,6 +65,7 @@ int mf2_lds_bytes(int S, int split)
 template <int S, bool SPLIT, bool HWR>
 __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
 {
+  static_assert(S == 4, "mf2_kernel: four streams per group (a sampler wave carries two, one per half)");
   extern __shared__ uint4 lds4[];
   unsigned char *lds = (unsigned char *)lds4;
   using L = Mf2Lds<S>;
@@ -126,24 +126,13 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
     /* group g's inputs of a frame: its conditioning (lane-private LDS
      * entries) and this wave's range word */
     auto stage = [&](int g, const FrameCond *cf, int par) {
-      bool in_range = true;
-      float *cg = cnd + g * GA_ROWS * S;
-      for (int s = 0; s < S; s++) {
-        const int sid = min(s0 + g * S + s, A.nstreams - 1);
-        const float *ca = gru_a_cond_of(cf, A, sid);
-        const float cz = ca[i], cr = ca[NA + i], ch = ca[2 * NA + i];
-        cg[tid * S + s] = cz;
-        cg[(NA + tid) * S + s] = cr;
-        cg[(2 * NA + tid) * S + s] = ch;
-        in_range &= fabsf(st[g][s]) <= 2.f && fabsf(cz) <= A.mf_zr_bound && fabsf(cr) <= A.mf_zr_bound &&
-                    fabsf(ch) <= A.mf_h_bound;
-      }
+      const bool in_range = ga_stage_cond<S>(A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
       if (lane == 0) okw[(par * 2 + g) * 8 + wv] = __ballot(!in_range) == 0ull;
     };
     const FrameCond *cf = A.cond;
     stage(0, cf, 0);
     stage(1, cf, 0);
-    if (tid < GB_ROWS) gbr[tid] = cvt_rne(A.gb_par[GB_ROWS + tid] * kScale) + A.gb_wsum[GB_ROWS + tid];
+    if (tid < GB_ROWS) gbr[tid] = gb_rec_seed(A, tid);
     uint32_t wz[MF_ZMAX], wr[MF_ZMAX], wh[MF_HMAX], oz[MF_ZMAX / 2], orr[MF_ZMAX / 2], oh[MF_HMAX / 2];
     {
       const uint32_t *mt = A.mf + (size_t)wv * MF_LANE_U32 * 64 + lane;
@@ -170,16 +159,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
     }
     const int nzr = A.mf_nzr[wv], nh = A.mf_nh[wv];
     const int nfzr = SPLIT ? A.mf_nfzr[wv] : 0, nfh = SPLIT ? A.mf_nfh[wv] : 0;
-    /* split models: the rows of this lane's hosted pieces (9 bits per gate,
-     * NA: none) and whether this thread's own unit has pieces to merge (bits
-     * 27..29), as in mf_kernel */
-    uint32_t frow = 0;
-    if constexpr (SPLIT) {
-      const uint32_t *fro = (const uint32_t *)A.mf_frow + tid;
-      const uint32_t e0 = fro[0], e1 = fro[SAMPLE_THREADS], e2 = fro[2 * SAMPLE_THREADS];
-      frow = (e0 & 0x1FF) | (e1 & 0x1FF) << 9 | (e2 & 0x1FF) << 18 | (e0 >> 16 & 1) << 27 | (e1 >> 16 & 1) << 28 |
-             (e2 >> 16 & 1) << 29;
-    }
+    uint32_t frow = 0; /* split models: this lane's hosted rows and merge bits */
+    if constexpr (SPLIT) frow = mf_frow_pack(A.mf_frow, tid, SAMPLE_THREADS);
     __syncthreads(); /* image in LDS */
     for (int g = 0; g < 2; g++)
       for (int s = 0; s < S; s++) xa[(g * S + s) * MF_XSTR + i] = (unsigned char)quant_s8_state(st[g][s]);
@@ -393,35 +374,24 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
     /* GRU_B input tiles in registers, the recurrent ones in LDS */
     v4i wt[MF_GB_IN];
 #pragma unroll
-    for (int t = 0; t < MF_GB_IN; t++) {
-      const uint4 u = A.mf_gb[t * 64 + lane];
-      wt[t] = v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
-    }
+    for (int t = 0; t < MF_GB_IN; t++) wt[t] = gb_tile(A, t * 64 + lane);
     if (sw == 0)
-      for (int q = 0; q < 3; q++) {
-        const uint4 u = A.mf_gb[(MF_GB_IN + q) * 64 + lane];
-        gbw[q * 64 + lane] = v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
-      }
-    /* this wave's GRU_B input seeds of group g for a frame (nnet.c:347-356
-     * with the offset-128 correction), and group g's LPC of that frame */
+      for (int q = 0; q < 3; q++) gbw[q * 64 + lane] = gb_tile(A, (MF_GB_IN + q) * 64 + lane);
+    /* this wave's GRU_B input seeds of group g for a frame, and group g's
+     * LPC of that frame */
     int *myg = gbs + sw * 2 * S * GB_ROWS;
     auto stage_frame = [&](int g, const FrameCond *cf) {
       for (int e = lane; e < S * GB_ROWS; e += 64) {
         const int s = e / GB_ROWS, r = e % GB_ROWS;
-        myg[g * S * GB_ROWS + e] =
-            cvt_rne((A.gb_par[r] + gru_b_cond_of(cf, A, min(s0 + g * S + s, A.nstreams - 1))[r]) * kScale) + A.gb_wsum[r];
+        myg[g * S * GB_ROWS + e] = gb_in_seed(A, cf, min(s0 + g * S + s, A.nstreams - 1), r);
       }
       if (samp_w && hl < NLPC) lpcb[(g * S + ms) * NLPC + hl] = lpc_of(cf, A, min(s0 + g * S + ms, A.nstreams - 1))[hl];
     };
-    auto ix_word = [](int su, int pu, int exc) { return make_int4(su * (GA_ROWS * 4), pu * (GA_ROWS * 4), exc * (GA_ROWS * 4), 0); };
     /* pred and the u-law indices of group g's next sample (lpcnet.c:252-254)
      * from the frame's LPC */
     auto restart = [&](int g) {
-      float p2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < NLPC; j++) p2 = p2 - lsr[g][j] * lpcb[(g * S + msc) * NLPC + j];
-      pred[g] = p2;
-      if (samp_w && hl == 0) *(int4 *)(ix + (g * S + ms) * 4) = ix_word(lin2ulaw_x86(lsr[g][0]), lin2ulaw_x86(pred[g]), last_exc[g]);
+      pred[g] = first_pred(lsr[g], lpcb + (g * S + msc) * NLPC);
+      if (samp_w && hl == 0) *(int4 *)(ix + (g * S + ms) * 4) = ix_word<S>(lin2ulaw_x86(lsr[g][0]), lin2ulaw_x86(pred[g]), last_exc[g]);
     };
     const FrameCond *cfr[2] = {A.cond, A.cond};
     stage_frame(0, cfr[0]);
@@ -494,17 +464,14 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
       }
       /* (the select-free walk of mf_kernel measured 1 % slower here) */
       const WalkOut R = dual_fc_walk<false, false, HWR>(F, t03, t47, xv, pred[g], lsr[g], lpr, nullptr, deemph[g]);
-      if (samp_w && hl == 0) *(int4 *)(ix + (g * S + ms) * 4) = ix_word(R.su, R.pu, R.exc);
+      if (samp_w && hl == 0) *(int4 *)(ix + (g * S + ms) * 4) = ix_word<S>(R.su, R.pu, R.exc);
       /* bookkeeping (lpcnet.c:262-269) and the output sample */
 #pragma unroll
       for (int j = NLPC - 1; j > 0; j--) lsr[g][j] = lsr[g][j - 1];
       lsr[g][0] = R.pcm;
       last_exc[g] = R.exc;
       pred[g] = R.pn;
-      float o = R.pcm + kPreemph * deemph[g];
-      deemph[g] = o;
-      if (o < -32767) o = -32767;
-      if (o > 32767) o = 32767;
+      const float o = out_sample(R.pcm, deemph[g], deemph[g]);
       const int sid = s0 + g * S + ms;
       if (samp_w && hl == 0 && sid < A.nstreams)
         A.pcm[((size_t)f * A.nstreams + sid) * A.N + n] = my_act[g] ? (short)round_half_up(o) : (short)0;
@@ -548,21 +515,20 @@ static int launch_mf2_t(const SampleArgs &a, hipStream_t stream)
 {
   if (ensure_dyn_lds((const void *)mf2_kernel<S, SPLIT, HWR>, 160 * 1024 - IMG_VAR)) return -1;
   const int grid = (a.nstreams + 2 * S - 1) / (2 * S);
-  hipLaunchKernelGGL((mf2_kernel<S, SPLIT, HWR>), dim3(grid), dim3(MF_THREADS), mf2_lds_bytes(S, SPLIT) - IMG_VAR, stream, a);
+  hipLaunchKernelGGL((mf2_kernel<S, SPLIT, HWR>), dim3(grid), dim3(MF_THREADS), mf2_lds_bytes(SPLIT) - IMG_VAR, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template <bool HWR>
-static int launch_mf2_h(const SampleArgs &a, int S, hipStream_t st)
+static int launch_mf2_h(const SampleArgs &a, hipStream_t st)
 {
-  if (a.mf_split) return S == 4 ? launch_mf2_t<4, true, HWR>(a, st) : launch_mf2_t<2, true, HWR>(a, st);
-  return S == 4 ? launch_mf2_t<4, false, HWR>(a, st) : launch_mf2_t<2, false, HWR>(a, st);
+  return a.mf_split ? launch_mf2_t<4, true, HWR>(a, st) : launch_mf2_t<4, false, HWR>(a, st);
 }
 
-int launch_mf2(const SampleArgs &a, int S, void *stream)
+int launch_mf2(const SampleArgs &a, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
-  return a.rcp_hw ? launch_mf2_h<true>(a, S, st) : launch_mf2_h<false>(a, S, st);
+  return a.rcp_hw ? launch_mf2_h<true>(a, st) : launch_mf2_h<false>(a, st);
 }
 
 }  // namespace lpcnet_mi355x

@@ -1,6 +1,6 @@
 /*
- * mf_common.h -- matrix-core building blocks shared by the two int8 sample
- * kernels (mf_kernel.hip, mfp_kernel.hip): register-resident GRU_A weight
+ * mf_common.h -- matrix-core building blocks shared by the int8 sample
+ * kernels (mf_kernel.hip, mf2_kernel.hip, mfw_kernel.hip): register-resident GRU_A weight
  * slots driven through v_mfma_i32_4x4x4_16b_i8 with LDS x words addressed by
  * packed 16-bit offsets, and the v_mfma_i32_16x16x64_i8 GRU_B tiles.
  */
@@ -517,6 +517,71 @@ __device__ __forceinline__ void ga_elementwise_staged(float (&st)[S], float (&e)
 __device__ __forceinline__ v4i mfma16(const v4i &w, const v4i &x, v4i acc)
 {
   return __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x, acc, 0, 0, 0);
+}
+
+/* ---- once per launch or frame, shared by mf_kernel, mf2_kernel and
+ * mfw_kernel where sharing leaves the kernel as it was.  The per-sample
+ * loops are each kernel's own; so are the activity check, a lane's GRU_A
+ * register tables, the sampler role geometry and the sampler state's load
+ * and store (profiles/r16: their shared forms moved mf_kernel's VGPR counts,
+ * spills or speed). ---- */
+
+/* a frame's GRU_A conditioning of unit i for the S streams from sg (a
+ * group's first stream), into LDS by lane position: cg[gate][tid][stream]
+ * (conflict-free reads, from the unit's column; read by this thread only).
+ * Returns whether the states and the conditioning are within the host's
+ * range bounds (SampleArgs::mf_zr_bound); NaN fails every compare: such a
+ * workgroup takes the exact path.  The caller ballots it into its range
+ * word. */
+template <int S>
+__device__ __forceinline__ bool ga_stage_cond(const SampleArgs &A, const FrameCond *cf, int sg, int i, int tid,
+                                              const float (&st)[S], float *cg)
+{
+  bool in_range = true;
+#pragma unroll
+  for (int s = 0; s < S; s++) {
+    const int sid = min(sg + s, A.nstreams - 1);
+    const float *ca = gru_a_cond_of(cf, A, sid);
+    const float cz = ca[i], cr = ca[NA + i], ch = ca[2 * NA + i];
+    cg[tid * S + s] = cz;
+    cg[(NA + tid) * S + s] = cr;
+    cg[(2 * NA + tid) * S + s] = ch;
+    in_range &= fabsf(st[s]) <= 2.f && fabsf(cz) <= A.mf_zr_bound && fabsf(cr) <= A.mf_zr_bound &&
+                fabsf(ch) <= A.mf_h_bound;
+  }
+  return in_range;
+}
+
+/* split models: the rows this thread's hosted pieces belong to (9 bits per
+ * gate; NA, or mfw_kernel's MFW_NOROW: none) and per gate whether the
+ * thread's own unit has hosted pieces to merge (bits 27..29), in one
+ * register for the whole launch; frow [3][stride] */
+__device__ __forceinline__ uint32_t mf_frow_pack(const int *frow, int tid, int stride)
+{
+  const uint32_t *fro = (const uint32_t *)frow + tid;
+  const uint32_t e0 = fro[0], e1 = fro[stride], e2 = fro[2 * stride];
+  return (e0 & 0x1FF) | (e1 & 0x1FF) << 9 | (e2 & 0x1FF) << 18 | (e0 >> 16 & 1) << 27 | (e1 >> 16 & 1) << 28 |
+         (e2 >> 16 & 1) << 29;
+}
+
+/* GRU_B accumulator seeds (nnet.c:347-356 with the offset-128 correction:
+ * cvt_rne((bias + cond) * SCALE) + 128 rowsum(w)): row r of the input
+ * product for stream sid in a frame, and of the recurrent product */
+__device__ __forceinline__ int gb_in_seed(const SampleArgs &A, const FrameCond *cf, int sid, int r)
+{
+  return cvt_rne((A.gb_par[r] + gru_b_cond_of(cf, A, sid)[r]) * kScale) + A.gb_wsum[r];
+}
+
+__device__ __forceinline__ int gb_rec_seed(const SampleArgs &A, int r)
+{
+  return cvt_rne(A.gb_par[GB_ROWS + r] * kScale) + A.gb_wsum[GB_ROWS + r];
+}
+
+/* entry e = tile * 64 + lane of the GRU_B weight tiles (input 18, recurrent 3) */
+__device__ __forceinline__ v4i gb_tile(const SampleArgs &A, int e)
+{
+  const uint4 u = A.mf_gb[e];
+  return v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
 }
 
 

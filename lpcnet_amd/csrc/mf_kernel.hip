@@ -241,12 +241,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
      * hosted pieces to merge (bits 27..29), in one register for the whole
      * launch */
     uint32_t frow = 0;
-    if constexpr (SPLIT) {
-      const uint32_t *fro = (const uint32_t *)A.mf_frow + tid;
-      const uint32_t e0 = fro[0], e1 = fro[SAMPLE_THREADS], e2 = fro[2 * SAMPLE_THREADS];
-      frow = (e0 & 0x1FF) | (e1 & 0x1FF) << 9 | (e2 & 0x1FF) << 18 | (e0 >> 16 & 1) << 27 | (e1 >> 16 & 1) << 28 |
-             (e2 >> 16 & 1) << 29;
-    }
+    if constexpr (SPLIT) frow = mf_frow_pack(A.mf_frow, tid, SAMPLE_THREADS);
 
     __syncthreads(); /* image in LDS */
     bool fast = true;
@@ -593,7 +588,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
 
     float lsr[NLPC], lpr[NLPC];
     float pred = 0.f, deemph = 0.f;
-    uint32_t rz = 0, rw = 0, rj = 0, rc = 0;
+    uint32_t rng[4] = {0, 0, 0, 0};
     int last_exc = 0;
     {
       const StreamState *p = &A.st[min(s0 + ms, A.nstreams - 1)];
@@ -604,7 +599,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
       }
       deemph = p->deemph_mem;
       last_exc = p->last_exc & 0xFF; /* the gathers index 256-row tables: never out of bounds (restore_state also rejects such snapshots) */
-      rz = p->rng[0]; rw = p->rng[1]; rj = p->rng[2]; rc = p->rng[3];
+      rng[0] = p->rng[0]; rng[1] = p->rng[1]; rng[2] = p->rng[2]; rng[3] = p->rng[3];
     }
     float sbv = A.st[min(s0 + sl, A.nstreams - 1)].gru_b_state[gu];
     /* the walk's select-free tanh: dual-FC node sums bounded by the model
@@ -618,15 +613,9 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
     constexpr int kRegTiles = kGbwLds ? MF_GB_IN : MF_GB_TILES;
     v4i wt[kRegTiles];
 #pragma unroll
-    for (int t = 0; t < kRegTiles; t++) {
-      const uint4 u = A.mf_gb[t * 64 + lane];
-      wt[t] = v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
-    }
+    for (int t = 0; t < kRegTiles; t++) wt[t] = gb_tile(A, t * 64 + lane);
     if (kGbwLds && sw == 0)
-      for (int g = 0; g < 3; g++) {
-        const uint4 u = A.mf_gb[(MF_GB_IN + g) * 64 + lane];
-        gbw[g * 64 + lane] = v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
-      }
+      for (int g = 0; g < 3; g++) gbw[g * 64 + lane] = gb_tile(A, (MF_GB_IN + g) * 64 + lane);
     auto put_xb = [&]() {
       if (gown) xb[gs * NB + gu] = (unsigned char)quant_s8_state(sbv);
     };
@@ -634,19 +623,10 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
     FcLane F;
     F.init(img, lane);
     put_xb();
-    /* the sig/pred/exc indices as the GRU_A waves consume them: at S > 1
-     * the byte offsets of the three embedding rows (the gathers add the lane
-     * offset only), at S = 1 the indices */
-    auto ix_word = [](int su, int pu, int exc) {
-      return S > 1 ? make_int4(su * (GA_ROWS * 4), pu * (GA_ROWS * 4), exc * (GA_ROWS * 4), 0) : make_int4(su, pu, exc, 0);
-    };
     if (samp) {
       /* pred and the u-law indices of the first sample (lpcnet.c:252-254) */
-      float p2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < NLPC; j++) p2 = p2 - lsr[j] * lpr[j];
-      pred = p2;
-      if (samp_w && hl == 0) *(int4 *)(ix + ms * 4) = ix_word(lin2ulaw_x86(lsr[0]), lin2ulaw_x86(pred), last_exc);
+      pred = first_pred(lsr, lpr);
+      if (samp_w && hl == 0) *(int4 *)(ix + ms * 4) = ix_word<S>(lin2ulaw_x86(lsr[0]), lin2ulaw_x86(pred), last_exc);
     }
     __syncthreads(); /* initial q(h_A), q(h_B), ix, seeds */
     stamp_start();
@@ -666,10 +646,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
       lsr[0] = pend_pcm;
         last_exc = pend_exc;
       pred = pend_pred;
-      float o = pend_pcm + kPreemph * deemph;
-      deemph = o;
-      if (o < -32767) o = -32767;
-      if (o > 32767) o = 32767;
+      const float o = out_sample(pend_pcm, deemph, deemph);
       if (samp_w && hl == 0 && pend_n >= A.preload) pcmbuf[ms * FRAME + pend_n] = (short)round_half_up(o);
       put_xb();
       pend_n = -1;
@@ -691,8 +668,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
           for (int j = 1; j < NLPC; j++) lpd[j] = lsr[j - 1] * lpr[j];
           stamp(13);
           /* the two kiss99 draws of this sample and their thresholds (nnet.c:178-184) */
-          const uint32_t r0 = kiss99_next(rz, rw, rj, rc);
-          const uint32_t r1 = kiss99_next(rz, rw, rj, rc);
+          const uint32_t r0 = kiss99_next(rng[0], rng[1], rng[2], rng[3]);
+          const uint32_t r1 = kiss99_next(rng[0], rng[1], rng[2], rng[3]);
           lane_thresholds(F, logit_tab, r0, r1, t03, t47);
           /* GRU_B recurrent product (nnet.c:355-361) needs only q(h_B(n-1)):
            * before barrier Y.  Seeds are the accumulator inputs. */
@@ -764,7 +741,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
                                    : dual_fc_walk_p<TRACE, false, HWR>(F, t03, t47, xv, pred, lpd, lpr, teach, deemph);
 #endif
         stamp(11);
-        if (samp_w && hl == 0 && n + 1 < A.N) *(int4 *)(ix + ms * 4) = ix_word(R.su, R.pu, R.exc);
+        if (samp_w && hl == 0 && n + 1 < A.N) *(int4 *)(ix + ms * 4) = ix_word<S>(R.su, R.pu, R.exc);
         if (tracing && samp_w && hl < 8 && my_active) {
           float v = R.lg[0];
 #pragma unroll
@@ -792,11 +769,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
         const float *lp = lpc_of(cf, A, min(s0 + msf, A.nstreams - 1));
 #pragma unroll
         for (int j = 0; j < NLPC; j++) lpr[j] = lp[j];
-        float p2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NLPC; j++) p2 = p2 - lsr[j] * lpr[j];
-        pred = p2;
-        if (samp_w && hl == 0) *(int4 *)(ix + ms * 4) = ix_word(lin2ulaw_x86(lsr[0]), lin2ulaw_x86(pred), last_exc);
+        pred = first_pred(lsr, lpr);
+        if (samp_w && hl == 0) *(int4 *)(ix + ms * 4) = ix_word<S>(lin2ulaw_x86(lsr[0]), lin2ulaw_x86(pred), last_exc);
       }
     }
     if (samp) finish();
@@ -809,7 +783,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
       for (int j = 0; j < NLPC; j++) p->last_sig[j] = lsr[j];
       p->deemph_mem = deemph;
       p->last_exc = last_exc;
-      p->rng[0] = rz; p->rng[1] = rw; p->rng[2] = rj; p->rng[3] = rc;
+      p->rng[0] = rng[0]; p->rng[1] = rng[1]; p->rng[2] = rng[2]; p->rng[3] = rng[3];
     }
     if (gact) A.st[s0 + gs].gru_b_state[gu] = sbv;
   }

@@ -506,32 +506,14 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
     /* group g's inputs of a frame: its conditioning (lane-private LDS
      * entries) and this wave's range word */
     auto stage = [&](int g, const FrameCond *cf, int par) {
-      bool in_range = true;
-      float *cg = cnd + g * GA_ROWS * S;
-#pragma unroll
-      for (int s = 0; s < S; s++) {
-        const int sid = min(s0 + g * S + s, A.nstreams - 1);
-        const float *ca = gru_a_cond_of(cf, A, sid);
-        const float cz = ca[i], cr = ca[NA + i], ch = ca[2 * NA + i];
-        cg[tid * S + s] = cz;
-        cg[(NA + tid) * S + s] = cr;
-        cg[(2 * NA + tid) * S + s] = ch;
-        in_range &= fabsf(st[g][s]) <= 2.f && fabsf(cz) <= A.mf_zr_bound && fabsf(cr) <= A.mf_zr_bound &&
-                    fabsf(ch) <= A.mf_h_bound;
-      }
+      const bool in_range = ga_stage_cond<S>(A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
       if (lane == 0) okw[(par * MFW_G + g) * 8 + wv] = __ballot(!in_range) == 0ull;
     };
 #pragma unroll
     for (int g = 0; g < MFW_G; g++) stage(g, A.cond, 0);
-    /* split form: this thread's part rows (9 bits per gate) and whether its
-     * unit has pieces there (bits 27..29), one register for the launch */
-    uint32_t frow = 0;
+    uint32_t frow = 0; /* split form: this thread's part rows and merge bits */
     if constexpr (SPLIT) {
-      constexpr int FS = SAMPLE_THREADS + 64 * MFW_H_WAVES;
-      const int *fro = A.mfw_frow + tid;
-      const uint32_t e0 = fro[0], e1 = fro[FS], e2 = fro[2 * FS];
-      frow = (e0 & 0x1FF) | (e1 & 0x1FF) << 9 | (e2 & 0x1FF) << 18 | (e0 >> 16 & 1) << 27 | (e1 >> 16 & 1) << 28 |
-             (e2 >> 16 & 1) << 29;
+      frow = mf_frow_pack(A.mfw_frow, tid, SAMPLE_THREADS + 64 * MFW_H_WAVES);
       for (int e = tid; e < MFW_PRT / 4; e += SAMPLE_THREADS) prt[e] = 0;
     }
     __syncthreads(); /* image in LDS */
@@ -679,39 +661,31 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
     sbv[g] = A.st[min(s0 + g * S + gs, A.nstreams - 1)].gru_b_state[gu];
   }
   /* GRU_B tiles (input 18 then recurrent 3) into LDS, the recurrent seeds */
-  for (int e = sw * 64 + lane; e < MF_GB_TILES * 64; e += 128) {
-    const uint4 u = A.mf_gb[e];
-    gbw[e] = v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
-  }
-  if (sw == 0 && lane < GB_ROWS) gbr[lane] = cvt_rne(A.gb_par[GB_ROWS + lane] * kScale) + A.gb_wsum[GB_ROWS + lane];
-  /* group g's GRU_B input seeds of a frame (nnet.c:347-356 with the
-   * offset-128 correction) and its LPC.  Each sampler wave stages its own
-   * two streams' seeds: the other wave may still be reading the group's
-   * previous ones, and a wave's GRU_B lanes of the other wave's streams are
-   * never used (gown) */
+  for (int e = sw * 64 + lane; e < MF_GB_TILES * 64; e += 128) gbw[e] = gb_tile(A, e);
+  if (sw == 0 && lane < GB_ROWS) gbr[lane] = gb_rec_seed(A, lane);
+  /* group g's GRU_B input seeds of a frame and its LPC.  Each sampler wave
+   * stages its own two streams' seeds: the other wave may still be reading
+   * the group's previous ones, and a wave's GRU_B lanes of the other wave's
+   * streams are never used (gown) */
   auto stage_frame = [&](int g, const FrameCond *cf) {
     for (int e = lane; e < S * GB_ROWS; e += 64) {
       const int s = e / GB_ROWS, rr = e % GB_ROWS;
       if ((s >> 1) != sw) continue;
-      gbs[g * S * GB_ROWS + e] =
-          cvt_rne((A.gb_par[rr] + gru_b_cond_of(cf, A, min(s0 + g * S + s, A.nstreams - 1))[rr]) * kScale) + A.gb_wsum[rr];
+      gbs[g * S * GB_ROWS + e] = gb_in_seed(A, cf, min(s0 + g * S + s, A.nstreams - 1), rr);
     }
     if (hl < NLPC) lpcb[(g * S + ms) * NLPC + hl] = lpc_of(cf, A, min(s0 + g * S + ms, A.nstreams - 1))[hl];
   };
-  auto ix_word = [](int su, int pu, int exc) { return make_int4(su * (GA_ROWS * 4), pu * (GA_ROWS * 4), exc * (GA_ROWS * 4), 0); };
   /* pred and the u-law indices of group g's next sample (lpcnet.c:252-254)
    * from the history and the frame's LPC */
   auto restart = [&](int g) {
     const float *ls = lsrb + (g * S + ms) * NLPC, *lp = lpcb + (g * S + ms) * NLPC;
     uint32_t *ss = sst + (g * S + ms) * 8;
-    float p2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NLPC; j++) p2 = p2 - ls[j] * lp[j];
+    const float p2 = first_pred(ls, lp);
     const int le = (int)ss[6];
     __builtin_amdgcn_wave_barrier();
     if (hl == 0) {
       ss[5] = __float_as_uint(p2);
-      *(int4 *)(ix + (g * S + ms) * 4) = ix_word(lin2ulaw_x86(ls[0]), lin2ulaw_x86(p2), le);
+      *(int4 *)(ix + (g * S + ms) * 4) = ix_word<S>(lin2ulaw_x86(ls[0]), lin2ulaw_x86(p2), le);
     }
   };
 #pragma unroll
@@ -830,12 +804,10 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
     const WalkOut R = dual_fc_walk_p<false, false, true>(F, t03, t47, xv, pred, lprod, lpr, nullptr, deemph0);
     MFW_SEC(4);
     /* bookkeeping (lpcnet.c:262-269) and the output sample */
-    float o = R.pcm + kPreemph * deemph0;
-    const float dn = o;
-    if (o < -32767) o = -32767;
-    if (o > 32767) o = 32767;
+    float dn;
+    const float o = out_sample(R.pcm, deemph0, dn);
     if (hl == 0) {
-      *(int4 *)(ix + (g * S + ms) * 4) = ix_word(R.su, R.pu, R.exc);
+      *(int4 *)(ix + (g * S + ms) * 4) = ix_word<S>(R.su, R.pu, R.exc);
       ls[0] = R.pcm;
       ss[0] = rz; ss[1] = rw; ss[2] = rj; ss[3] = rc;
       ss[4] = __float_as_uint(dn);

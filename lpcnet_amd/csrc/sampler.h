@@ -264,6 +264,40 @@ __device__ __forceinline__ WalkOut dual_fc_walk(const FcLane &F, float t03, floa
   return dual_fc_walk_p<TRACE, FIN, HW, ST>(F, t03, t47, xv, pred, lprod, lpr, teach, deemph, st);
 }
 
+/* ---- the sampler waves' bookkeeping around the walk, shared by the
+ * matrix-core sample kernels (mf_kernel, mf2_kernel, mfw_kernel) ---- */
+
+/* the sig/pred/exc indices as the GRU_A waves consume them: at S > 1 the
+ * byte offsets of the three embedding rows (the gathers add the lane offset
+ * only), at S = 1 the indices */
+template <int S>
+__device__ __forceinline__ int4 ix_word(int su, int pu, int exc)
+{
+  return S > 1 ? make_int4(su * (GA_ROWS * 4), pu * (GA_ROWS * 4), exc * (GA_ROWS * 4), 0) : make_int4(su, pu, exc, 0);
+}
+
+/* pred of a frame's first sample (lpcnet.c:252-254) from the history and
+ * the frame's LPC (registers or LDS) */
+__device__ __forceinline__ float first_pred(const float *lsr, const float *lpr)
+{
+  float p2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NLPC; j++) p2 = p2 - lsr[j] * lpr[j];
+  return p2;
+}
+
+/* the output sample (lpcnet.c:266-269): de-emphasis, then the clamp to
+ * int16's symmetric range.  mem: the unclamped value, the next de-emphasis
+ * memory; returns the clamped one */
+__device__ __forceinline__ float out_sample(float pcm, float deemph, float &mem)
+{
+  float o = pcm + kPreemph * deemph;
+  mem = o;
+  if (o < -32767) o = -32767;
+  if (o > 32767) o = 32767;
+  return o;
+}
+
 }  // namespace lpcnet_mi355x
 
 #endif
