@@ -284,7 +284,9 @@ LPCNET_EXPORT int lpcnet_batch_set_rcp_table(LPCNetBatch *b, const uint32_t *tab
  * compensation[i % 18]) (freq.c:318, pow10_dd.h); op 10 _mm256_rcp_ps of a
  * Pade denominator (vec_avx.h:408,437, hardware form); op 11 / 12
  * sigmoid8_approx of the int8 gates' inputs (|x| < 2^18, device_math.h
- * sigmoid_x86_fin_n), hardware / table rcpps.
+ * sigmoid_x86_fin_n), hardware / table rcpps; op 13 / 14 tanh8_approx in its
+ * select-free form (finite |x| < 2^30, device_math.h tanh_x86_fin_n),
+ * hardware / table rcpps.
  * Returns 0, or -1 on bad arguments / HIP failure. */
 LPCNET_EXPORT int lpcnet_mi355x_device_numerics(int device, int op, const void *in, void *out, int n);
 /* Validate a weight blob with every rule lpcnet_load_model applies

@@ -286,10 +286,21 @@ __device__ __forceinline__ void tanh_x86_n(float (&X)[N], const uint32_t *tab)
   for (int k = 0; k < N; k++) X[k] = clamp_x86(num[k] * den[k], -1.f, 1.f);
 }
 
-/* tanh8_approx for finite inputs below 2^60 in magnitude: the Pade
- * denominator lies in [952.72, 2^125), so rcpps never flushes and no NaN
- * arises: rcp_x86 / clamp_x86 without their flush and NaN selects, identical
- * to tanh_x86_n for every such input (mf_kernel's bounded-input path). */
+/* The select-free tanh's domain: finite |X| < kTanhFinBound.  The Pade
+ * denominator is quartic in X (11.886 X^4 + ...): below 2^30 it stays under
+ * 11.89 * 2^120 < 2^124, while at |X| ~ 2^30.4 it passes 2^125, rcpps
+ * flushes to zero, and from |X| ~ 1.64e9 (2^30.6) the numerator is inf and
+ * the reference's result is inf * 0 = NaN.  The hosts' bounds (fc_fin,
+ * mf_h_bound in model_host.cpp) are built on this constant. */
+constexpr float kTanhFinBound = 1073741824.f; /* 2^30 */
+
+/* tanh8_approx for finite inputs below kTanhFinBound (2^30) in magnitude:
+ * X2 < 2^60, the Pade denominator lies in [952.72, 2^124), so rcpps never
+ * flushes and no NaN arises (the numerator, quintic in X, is +-inf from
+ * |X| ~ 2^25.7 on: times a positive normal reciprocal it stays +-inf and the
+ * clamp gives +-1, as on x86): rcp_x86 / clamp_x86 without their flush and NaN
+ * selects, identical to tanh_x86_n for every such input (mf_kernel's
+ * bounded-input path). */
 template <int N, bool HW = false, int TB = RCP_TABLE_BITS>
 __device__ __forceinline__ void tanh_x86_fin_n(float (&X)[N], const uint32_t *tab)
 {

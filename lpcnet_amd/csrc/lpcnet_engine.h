@@ -237,9 +237,10 @@ struct SampleArgs {
   float mf_zr_bound;                 /* |GRU_A z/r conditioning| below this (and finite) for a workgroup's
                                         streams: the elementwise step's range selects are dead (mf_kernel);
                                         negative: never */
-  float mf_h_bound;                  /* the same for the h gate's conditioning (tanh range) */
+  float mf_h_bound;                  /* the same for the h gate's conditioning (tanh range: the gate's
+                                        input stays below device_math.h's kTanhFinBound) */
   int fc_fin;                        /* every dual-FC node sum |bias| + 2 sum|w| is finite and below
-                                        2^59: with GRU_B states within [-2, 2] (int8 models keep them
+                                        kTanhFinBound (2^30): with GRU_B states within [-2, 2] (int8 models keep them
                                         there; checked per launch) the walk's tanh takes the
                                         select-free form */
   const float *mf_emb[3];            /* sig/pred/exc tables with columns in lane order:

@@ -127,7 +127,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
      * entries) and this wave's range word */
     auto stage = [&](int g, const FrameCond *cf, int par) {
       const bool in_range = ga_stage_cond<S>(A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
-      if (lane == 0) okw[(par * 2 + g) * 8 + wv] = __ballot(!in_range) == 0ull;
+      const bool wave_ok = __ballot(!in_range) == 0ull; /* every lane active: not inside the lane-0 branch */
+      if (lane == 0) okw[(par * 2 + g) * 8 + wv] = wave_ok;
     };
     const FrameCond *cf = A.cond;
     stage(0, cf, 0);

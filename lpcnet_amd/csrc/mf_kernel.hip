@@ -196,7 +196,9 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
         in_range &= fabsf(st[s]) <= 2.f && fabsf(cz) <= A.mf_zr_bound && fabsf(cr) <= A.mf_zr_bound &&
                     fabsf(ch) <= A.mf_h_bound;
       }
-      if (lane == 0) okw[wv] = __ballot(!in_range) == 0ull;
+      /* the ballot with every lane of the wave active: inside the lane-0 branch it sees lane 0 alone */
+      const bool wave_ok = __ballot(!in_range) == 0ull;
+      if (lane == 0) okw[wv] = wave_ok;
       for (int e = tid; e < S * GB_ROWS; e += SAMPLE_THREADS) {
         const int s = e / GB_ROWS, r = e % GB_ROWS;
         gbs[e] =
@@ -367,7 +369,8 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
         pcm_out += (size_t)A.nstreams * A.N;
       }
       /* every input of this frame within the host's range bounds
-       * (SampleArgs::mf_zr_bound): the elementwise step's range selects are
+       * (SampleArgs::mf_zr_bound, and mf_h_bound: the h gate's tanh input
+       * below kTanhFinBound): the elementwise step's range selects are
        * dead, take the select-free forms (uniform per workgroup) */
       fast = true;
       for (int w = 0; w < SAMPLE_WAVES; w++) fast &= okw[w] != 0;
@@ -603,7 +606,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
     }
     float sbv = A.st[min(s0 + sl, A.nstreams - 1)].gru_b_state[gu];
     /* the walk's select-free tanh: dual-FC node sums bounded by the model
-     * (fc_fin) for GRU_B states within [-2, 2]; int8 GRU_B updates keep a
+     * (fc_fin: below kTanhFinBound) for GRU_B states within [-2, 2]; int8 GRU_B updates keep a
      * state there (convex combinations of it and tanh outputs), so the
      * launch-time check covers the launch */
     const bool walk_fin = A.fc_fin && __builtin_amdgcn_readfirstlane((int)(__ballot(!(fabsf(sbv) <= 2.f)) == 0ull));

@@ -507,7 +507,8 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
      * entries) and this wave's range word */
     auto stage = [&](int g, const FrameCond *cf, int par) {
       const bool in_range = ga_stage_cond<S>(A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
-      if (lane == 0) okw[(par * MFW_G + g) * 8 + wv] = __ballot(!in_range) == 0ull;
+      const bool wave_ok = __ballot(!in_range) == 0ull; /* every lane active: not inside the lane-0 branch */
+      if (lane == 0) okw[(par * MFW_G + g) * 8 + wv] = wave_ok;
     };
 #pragma unroll
     for (int g = 0; g < MFW_G; g++) stage(g, A.cond, 0);

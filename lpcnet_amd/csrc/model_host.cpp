@@ -5,6 +5,8 @@
  */
 #include "model_host.h"
 
+#include "device_math.h" /* kTanhFinBound */
+
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -482,16 +484,27 @@ void build_lockstep_image(const Blob &B, const LoadEnv &env, HostModel &H)
   memcpy(&img[IMG_FCW], B.fc_w, 256 * 32 * 4);
   {
     /* dual-FC node sums (nnet.c:193-199) are bounded by |bias| + 2 sum|w|
-     * for GRU_B states within [-2, 2]: far below 2^60 and finite, tanh8's
-     * flush and NaN selects are dead (tanh_x86_fin_n) */
+     * for GRU_B states within [-2, 2]: while that is finite and below
+     * kTanhFinBound (2^30; every partial sum of the kernel's float chain is
+     * bounded by it too), tanh8's flush and NaN selects are dead
+     * (tanh_x86_fin_n).  Node 0 is never walked (nnet.c:190: i = (1 << b) | val)
+     * but is bounded like the rest. */
     bool fin = true;
-    for (int c = 0; c < 2 && fin; c++)
-      for (int i = 0; i < 256 && fin; i++) {
+    double worst = 0;
+    for (int c = 0; c < 2; c++)
+      for (int i = 0; i < 256; i++) {
         double bd = fabs((double)B.fc_b[c * 256 + i]);
         for (int j = 0; j < 16; j++) bd += 2.0 * fabs((double)B.fc_w[i * 32 + c * 16 + j]);
-        fin = std::isfinite(bd) && bd < 0x1p59;
+        fin = fin && std::isfinite(bd) && bd < (double)kTanhFinBound;
+        worst = std::isfinite(bd) ? std::max(worst, bd) : INFINITY;
       }
     sa.fc_fin = fin && !env.fc_exact ? 1 : 0;
+    if (env.verbose) {
+      char line[160];
+      snprintf(line, sizeof line, "lpcnet: dual-FC walk: %s form (largest node bound %g, limit %g%s)\n",
+               sa.fc_fin ? "select-free" : "exact", worst, (double)kTanhFinBound, env.fc_exact ? ", exact forced" : "");
+      H.bounds_note += line;
+    }
   }
   memcpy(&img[IMG_FCB], B.fc_b, 512 * 4);
   memcpy(&img[IMG_FCF], B.fc_f, 512 * 4);
@@ -662,8 +675,11 @@ void build_matrix_core_tables(const Blob &B, const ModelBuildOpts &opts, const L
  * z/r: cvt_rne((bias + diag st + ((cond + Esig) + Epred) + Eexc) * 16256)
  * cannot leave int32 (x86: INT_MIN) while |that sum| < 2^31 / 16256, with
  * |st| <= 2 (restore-enforced); h: tanh's Pade denominator cannot overflow
- * nor go NaN while its input is finite and < 2^60.  The kernel checks a
- * workgroup's conditioning against these bounds once per launch. */
+ * nor go NaN while its input -- (bias + diag st + recurrent sum) r + (cond +
+ * embeddings) -- is finite and below kTanhFinBound (2^30): the int8
+ * recurrent sum is an int32 x 2^-14, below 2^17 in magnitude, and r lies in
+ * [0, 1].  The kernel checks a workgroup's conditioning against these bounds
+ * once per launch. */
 void build_range_bounds(const LoadEnv &env, HostModel &H)
 {
   SampleArgs &sa = H.sa;
@@ -690,7 +706,7 @@ void build_range_bounds(const LoadEnv &env, HostModel &H)
     }
     (g < 2 ? ez : eh) = std::max(g < 2 ? ez : eh, e);
   }
-  const double zr = 0.99 * (2147483648.0 / 16256.0) - bz - ez, hb = 1e17 - bh - eh;
+  const double zr = 0.99 * (2147483648.0 / 16256.0) - bz - ez, hb = (double)kTanhFinBound - 0x1p17 - bh - eh;
   sa.mf_zr_bound = finite && zr > 0 ? (float)zr : -1.f;
   sa.mf_h_bound = finite && hb > 0 ? (float)hb : -1.f;
   if (env.mf_exact) sa.mf_zr_bound = sa.mf_h_bound = -1.f;
@@ -699,7 +715,7 @@ void build_range_bounds(const LoadEnv &env, HostModel &H)
     char line[200];
     snprintf(line, sizeof line, "lpcnet: GRU_A range bounds: z/r %g (bias+diag %g, embeddings %g), h %g\n", sa.mf_zr_bound, bz,
              ez, sa.mf_h_bound);
-    H.bounds_note = line;
+    H.bounds_note += line;
   }
 }
 

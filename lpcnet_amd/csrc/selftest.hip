@@ -75,6 +75,19 @@ __global__ void numerics_kernel(int op, const uint32_t *__restrict__ in, uint32_
       out[e] = __float_as_uint(v[0]);
       break;
     }
+    case 13: {
+      /* the select-free tanh: finite inputs |x| < kTanhFinBound only */
+      float v[1] = {x};
+      tanh_x86_fin_n<1, true>(v, rcp);
+      out[e] = __float_as_uint(v[0]);
+      break;
+    }
+    case 14: {
+      float v[1] = {x};
+      tanh_x86_fin_n<1, false>(v, rcp); /* the table form */
+      out[e] = __float_as_uint(v[0]);
+      break;
+    }
     default: out[e] = 0; break;
   }
 }
@@ -85,7 +98,7 @@ using namespace lpcnet_mi355x;
 
 extern "C" LPCNET_EXPORT int lpcnet_mi355x_device_numerics(int device, int op, const void *in, void *out, int n)
 {
-  if (op < 0 || op > 12 || n < 0 || (n > 0 && (!in || !out))) return -1;
+  if (op < 0 || op > 14 || n < 0 || (n > 0 && (!in || !out))) return -1;
   if (n == 0) return 0;
   if (hipSetDevice(device) != hipSuccess) return -1;
   const size_t nin = op == 8 ? 4 : (size_t)n;

@@ -721,6 +721,38 @@ void oracle_get_conv_mem(const OracleState *st, float *c1, float *c2)
   if (c2) memcpy(c2, st->conv2_mem, sizeof(st->conv2_mem));
 }
 
+void oracle_get_tail(const OracleState *st, float *last_sig, float *deemph_mem, int *last_exc, uint32_t *rng)
+{
+  if (last_sig) memcpy(last_sig, st->last_sig, sizeof(st->last_sig));
+  if (deemph_mem) *deemph_mem = st->deemph_mem;
+  if (last_exc) *last_exc = st->last_exc;
+  if (rng) {
+    rng[0] = st->rng.z;
+    rng[1] = st->rng.w;
+    rng[2] = st->rng.jsr;
+    rng[3] = st->rng.jcong;
+  }
+}
+
+void oracle_set_tail(OracleState *st, const float *last_sig, float deemph_mem, int last_exc, const uint32_t *rng)
+{
+  if (last_sig) memcpy(st->last_sig, last_sig, sizeof(st->last_sig));
+  st->deemph_mem = deemph_mem;
+  st->last_exc = last_exc;
+  if (rng) {
+    st->rng.z = rng[0];
+    st->rng.w = rng[1];
+    st->rng.jsr = rng[2];
+    st->rng.jcong = rng[3];
+  }
+}
+
+void oracle_set_state(OracleState *st, const float *gru_a_state, const float *gru_b_state)
+{
+  if (gru_a_state) memcpy(st->gru_a_state, gru_a_state, sizeof(st->gru_a_state));
+  if (gru_b_state) memcpy(st->gru_b_state, gru_b_state, sizeof(st->gru_b_state));
+}
+
 /* nnet.c:122-135 _lpcnet_compute_dense (all row counts here are multiples of 16) */
 static void dense(const OracleState *st, float *out, const float *w, const float *b, int nin, int nout, int tanh_act, const float *in)
 {

@@ -119,6 +119,12 @@ int oracle_frame_count(const OracleState *st);
 void oracle_get_state(const OracleState *st, float *gru_a_state /*384*/, float *gru_b_state /*16*/);
 /* The conv memories of run_frame_network (the inputs of the last two frames). */
 void oracle_get_conv_mem(const OracleState *st, float *conv1_mem /*168*/, float *conv2_mem /*256*/);
+/* The signal tail's state (lpcnet.c:235-271): last_sig, deemph_mem, last_exc
+ * and the four kiss99 words (z, w, jsr, jcong); a NULL pointer leaves that
+ * part alone. */
+void oracle_get_tail(const OracleState *st, float *last_sig /*16*/, float *deemph_mem, int *last_exc, uint32_t *rng /*4*/);
+void oracle_set_tail(OracleState *st, const float *last_sig /*16*/, float deemph_mem, int last_exc, const uint32_t *rng /*4*/);
+void oracle_set_state(OracleState *st, const float *gru_a_state /*384*/, const float *gru_b_state /*16*/);
 
 #ifdef __cplusplus
 }

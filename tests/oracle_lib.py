@@ -49,6 +49,9 @@ _SIGS = [
     ("oracle_state_restore", None, [_vp, _vp]),
     ("oracle_decode_packet", _i, [_vp, _vp, _vp]),
     ("oracle_decode", _i, [_vp, _vp, _vp]),
+    ("oracle_get_tail", None, [_vp, _vp, _vp, _vp, _vp]),
+    ("oracle_set_tail", None, [_vp, _vp, C.c_float, _i, _vp]),
+    ("oracle_set_state", None, [_vp, _vp, _vp]),
 ]
 RCP_TABLE = np.fromfile(os.path.join(GOLDEN, "rcp_x86.bin"), dtype=np.uint32)
 assert RCP_TABLE.size == 2048
@@ -246,6 +249,28 @@ class Oracle:
         b = np.zeros(16, np.float32)
         self._lib.oracle_get_state(self._st, a.ctypes.data, b.ctypes.data)
         return a, b
+
+    def tail(self):
+        """(last_sig [16], deemph_mem (float32), last_exc, rng [4] uint32) of
+        the signal tail (lpcnet.c:235-271)."""
+        sig = np.zeros(16, np.float32)
+        de = np.zeros(1, np.float32)
+        exc = C.c_int(0)
+        rng = np.zeros(4, np.uint32)
+        self._lib.oracle_get_tail(self._st, sig.ctypes.data, de.ctypes.data, C.addressof(exc), rng.ctypes.data)
+        return sig, de[0], exc.value, rng
+
+    def set_tail(self, last_sig, deemph_mem, last_exc: int, rng) -> None:
+        sig = np.ascontiguousarray(last_sig, np.float32)
+        r = np.ascontiguousarray(rng, np.uint32)
+        assert sig.size == 16 and r.size == 4
+        self._lib.oracle_set_tail(self._st, sig.ctypes.data, C.c_float(float(deemph_mem)), int(last_exc), r.ctypes.data)
+
+    def set_state(self, gru_a_state, gru_b_state) -> None:
+        a = np.ascontiguousarray(gru_a_state, np.float32)
+        b = np.ascontiguousarray(gru_b_state, np.float32)
+        assert a.size == 384 and b.size == 16
+        self._lib.oracle_set_state(self._st, a.ctypes.data, b.ctypes.data)
 
     def conv_mem(self):
         """(conv1 memory [168], conv2 memory [256]) of run_frame_network."""

@@ -394,6 +394,17 @@ def test_walk_exact_form_for_states_outside_the_bound(require_gpu, blobs, monkey
         outs.append(np.stack([b.synthesize(allf[f]) for f in range(4, F)], 1))
         b.close()
     assert np.array_equal(outs[0], outs[1])
+    # and both are what the reference computes from that state: the oracle with the same NaN written in
+    for s in (0, 1, 2):
+        o = O.Oracle(blob, 0)
+        for f in range(4):
+            o.synthesize(allf[f, s])
+        if s == 1:
+            a, g = o.state()
+            g[3] = np.nan
+            o.set_state(a, g)
+        want = np.stack([o.synthesize(allf[f, s]) for f in range(4, F)])
+        assert np.array_equal(outs[0][s], want), "stream %d differs from the oracle" % s
 
 
 def test_restore_refuses_out_of_range_last_exc(require_gpu, blobs):

@@ -103,6 +103,39 @@ def test_rcpps_every_prefix_and_exponent_on_device(require_gpu):
     assert bad.size == 0, f"{bad.size} mismatches, first den bits {bits[bad[:4]]}"
 
 
+TANH_FIN_BOUND = 2.0 ** 30  # device_math.h kTanhFinBound: the select-free tanh's documented domain is finite |x| below it
+
+
+@pytest.mark.parametrize("op", [13, 14], ids=["hw_rcp", "table"])
+def test_tanh_fin_on_device(require_gpu, op):
+    """tanh_x86_fin_n (the select-free tanh of the dual-FC walk, GRU_B's h
+    gate and mf_kernel's range-guarded GRU_A h gate) over its documented
+    domain, finite |x| < 2^30: the golden inputs inside it against the
+    reference's compiled tanh8_approx, and a geometric sweep of both signs
+    from 2^-20 to the bound -- 64 steps per octave, every power of two, and
+    the last float below the bound -- against op 0 (tanh_x86, pinned to the
+    reference by test_activations_bit_exact_on_device).  The Pade denominator
+    is quartic in x: it passes 2^125 near 2^30.4 and the reference is NaN from
+    1.64e9 on, which the select-free form (no NaN select, v_med3) cannot
+    give; up to the bound the two are the same function."""
+    x = np.ascontiguousarray(K["act_x"], np.float32)
+    keep = np.isfinite(x) & (np.abs(x) < TANH_FIN_BOUND)
+    assert keep.sum() > 40000
+    got = L.device_numerics(op, x[keep])
+    bad = np.flatnonzero(got != f32bits(K["act_tanh"])[keep])
+    assert bad.size == 0, f"{bad.size} mismatches with the reference, first x={x[keep][bad[:4]]}"
+    mag = np.exp2(np.arange(-20 * 64, 30 * 64) / 64.0).astype(np.float32)
+    mag = np.concatenate([mag, np.exp2(np.arange(-20, 30)).astype(np.float32),
+                          [np.nextafter(np.float32(TANH_FIN_BOUND), np.float32(0))]]).astype(np.float32)
+    assert mag.max() < TANH_FIN_BOUND and mag.max() == np.float32(1073741760.0)
+    sweep = np.concatenate([mag, -mag])
+    got, exp = L.device_numerics(op, sweep), L.device_numerics(0, sweep)
+    bad = np.flatnonzero(got != exp)
+    assert bad.size == 0, f"{bad.size} mismatches with tanh_x86, first x={sweep[bad[:4]]} got {got[bad[:4]]} expected {exp[bad[:4]]}"
+    # the sweep reaches the part of the domain where the numerator is +-inf and the clamp decides
+    assert (exp[np.abs(sweep) > 2.0 ** 26].view(np.float32) == np.sign(sweep[np.abs(sweep) > 2.0 ** 26])).all()
+
+
 def test_sigmoid_fin_on_device(require_gpu):
     """sigmoid_x86_fin_n (the int8 gates' sigmoid, inputs (float)int32 *
     2^-14 plus such a term: |x| < 2^18) against the reference's compiled
