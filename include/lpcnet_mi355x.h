@@ -201,8 +201,12 @@ LPCNET_EXPORT int lpcnet_batch_memcpy_d2h(LPCNetBatch *b, void *dst, const void 
  * 1 frame-network kernel (per-frame frame kernel, or chunk_kernel once per
  * run of frames), 2 the PLC predictor (lpcnet_batch_plc_predict*, timed
  * whenever enable > 0), 3 the feature extractor
- * (lpcnet_batch_compute_features*, one launch per frame, likewise).  Returns
- * total ms and the number of launches.
+ * (lpcnet_batch_compute_features*, one launch per frame, likewise), 4 the
+ * 1.6 kb/s encoder (lpcnet_batch_encode*, lpcnet_batch_compute_features4:
+ * the four analysis launches of a packet, one frame each, and the launches
+ * of enc_kernel.hip as one region; likewise), 5 the part of 4 that is
+ * enc_kernel.hip (four frames per region).  Returns total ms and the number
+ * of launches.
  * enable: 0 off, 1 events around the sample kernel only, 2 (or more) around
  * both kernels. */
 LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable);
@@ -473,9 +477,8 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
  * unchanged; lpcnet_batch_reset / _reset_stream zero it (lpcnet_encoder_init
  * inside lpcnet_plc_reset).
  * Out of scope: burg_cepstral_analysis, the PLC state machine,
- * process_superframe / lpcnet_encode / lpcnet_compute_features (the
- * four-frame quantisation), and drop-in LPCNetEncState handles (one stream
- * per launch is slower than the CPU).
+ * process_multi_frame and drop-in LPCNetEncState handles (one stream per
+ * launch is slower than the CPU).
  * Argument errors return -1 with the reason in lpcnet_mi355x_last_error. */
 /* lpcnet_compute_single_frame_features for every stream s with active[s] != 0
  * (NULL: all). pcm [B][160]; features [B][NB_TOTAL_FEATURES]. Inactive streams:
@@ -496,6 +499,44 @@ LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream /* -1: 
 LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *b);
 LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf);
 LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf);
+
+/* ---- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) -------------
+ * lpcnet_enc.c:882-909 for a whole batch: four analysis launches
+ * (feat_kernel.hip's superframe form) and process_superframe
+ * (enc_kernel.hip), bit-identical per stream to the reference's build with
+ * quantize = encode = 1 (lpcnet_encode) or 0 (lpcnet_compute_features).  A
+ * stream's encoder state is its analysis state above (the Viterbi rows are
+ * the single-frame path's: single-frame and four-frame calls on one stream
+ * behave as one LPCNetEncState does) plus the encoder's own vq_mem[18], which
+ * is not the decoder's; lpcnet_batch_reset, _reset_stream and
+ * _features_reset zero both.  Codebook distances of 1e15f or more, and NaN,
+ * are outside the contract (the reference then reads uninitialised indices);
+ * PCM input cannot produce them.  Inactive streams keep their state, packet
+ * and feature rows. */
+/* lpcnet_encode: pcm [B][640] -> packets [B][8]; features (NULL: not wanted)
+ * [4][B][NB_TOTAL_FEATURES] receives st->features after quantisation, what a
+ * decoder reconstructs plus its LPC.  Needs a model with the ceps codebooks. */
+LPCNET_EXPORT int lpcnet_batch_encode(LPCNetBatch *b, const short *pcm, unsigned char *packets, float *features,
+                                      const unsigned char *active);
+/* lpcnet_compute_features: unquantised; pcm [B][640] -> features
+ * [4][B][NB_TOTAL_FEATURES].  Needs no model. */
+LPCNET_EXPORT int lpcnet_batch_compute_features4(LPCNetBatch *b, const short *pcm, float *features, const unsigned char *active);
+/* device pointers, enqueued on the batch's stream: d_pcm [4 npackets][B][160]
+ * (what lpcnet_batch_synthesize_frames writes), d_packets [npackets][B][8]
+ * (what lpcnet_batch_decode_frames reads), d_features (NULL: not wanted)
+ * [4 npackets][B][row], row NB_FEATURES or NB_TOTAL_FEATURES; anything else -1. */
+LPCNET_EXPORT int lpcnet_batch_encode_device(LPCNetBatch *b, const short *d_pcm, unsigned char *d_packets, float *d_features,
+                                             int row, const unsigned char *d_active, int npackets);
+/* snapshots of one stream's encoder state: the features snapshot followed by vq_mem[18] */
+LPCNET_EXPORT int lpcnet_batch_encode_state_size(const LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_encode_save_state(LPCNetBatch *b, int stream, void *buf);
+LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, const void *buf);
+/* Host only: main_pitch of lpcnet_enc.c:678-679 for n values of center_pitch,
+ * from the threshold table the encoder kernel uses (the smallest float that
+ * reaches each main_pitch under the host's double log) and evaluated as the
+ * kernel evaluates it.  Non-finite and non-positive inputs give 0, as the
+ * x86 (int) cast does. */
+LPCNET_EXPORT int lpcnet_mi355x_enc_main_pitch(const float *center_pitch, int *out, int n);
 
 /* Last error string of this thread. */
 LPCNET_EXPORT const char *lpcnet_mi355x_last_error(void);

@@ -139,6 +139,14 @@ def _load():
         "lpcnet_batch_features_state_size": (i, [vp]),
         "lpcnet_batch_features_save_state": (i, [vp, i, vp]),
         "lpcnet_batch_features_restore_state": (i, [vp, i, vp]),
+        # 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features)
+        "lpcnet_batch_encode": (i, [vp, vp, vp, vp, vp]),
+        "lpcnet_batch_compute_features4": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_encode_device": (i, [vp, vp, vp, vp, i, vp, i]),
+        "lpcnet_batch_encode_state_size": (i, [vp]),
+        "lpcnet_batch_encode_save_state": (i, [vp, i, vp]),
+        "lpcnet_batch_encode_restore_state": (i, [vp, i, vp]),
+        "lpcnet_mi355x_enc_main_pitch": (i, [vp, vp, i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -267,6 +275,16 @@ def with_model_constants(blob: bytes, lpc_gamma: float | None = None, features_d
         head[20:20 + len(name)] = name.encode()
         out += head + val + bytes(60)
     return bytes(out)
+
+
+def enc_main_pitch(center_pitch: np.ndarray) -> np.ndarray:
+    """main_pitch of the 1.6 kb/s encoder (lpcnet_enc.c:678-679) for every
+    float32 center_pitch, from the kernel's threshold table (host only)."""
+    x = np.ascontiguousarray(center_pitch, np.float32).ravel()
+    out = np.zeros(x.size, np.int32)
+    if lib.lpcnet_mi355x_enc_main_pitch(x.ctypes.data, out.ctypes.data, x.size) != 0:
+        raise LPCNetError(last_error())
+    return out
 
 
 def synthetic_features(stream: int, nframes: int) -> np.ndarray:
@@ -701,6 +719,71 @@ class LPCNetBatch:
         if lib.lpcnet_batch_features_restore_state(self._b, stream, state) != 0:
             raise LPCNetError(last_error())
 
+    # -- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) ----------
+    def _pcm4(self, pcm: np.ndarray, active) -> tuple[np.ndarray, np.ndarray | None]:
+        p = np.ascontiguousarray(pcm)
+        if p.dtype != np.int16 or p.shape != (self.B, 4 * FRAME_SIZE):
+            raise ValueError(f"pcm must be int16 [{self.B}, {4 * FRAME_SIZE}]")
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        if a is not None and a.shape != (self.B,):
+            raise ValueError(f"active must be [{self.B}]")
+        return p, a
+
+    def _out4(self, out: np.ndarray | None) -> np.ndarray:
+        o = np.zeros((4, self.B, NB_TOTAL_FEATURES), np.float32) if out is None else out
+        if o.dtype != np.float32 or o.shape != (4, self.B, NB_TOTAL_FEATURES) or not o.flags.c_contiguous:
+            raise ValueError(f"features must be a contiguous float32 [4, {self.B}, {NB_TOTAL_FEATURES}]")
+        return o
+
+    def encode(self, pcm: np.ndarray, active: np.ndarray | None = None, packets: np.ndarray | None = None,
+               features: np.ndarray | None = None, want_features: bool = True):
+        """lpcnet_encode on every stream with active[s] != 0 (None: all): pcm
+        [B, 640] int16 -> (packets [B, 8] uint8, features [4, B, 36] or None):
+        st->features after quantisation.  Rows of inactive streams keep what
+        ``packets`` / ``features`` held (zeros without them).  Needs a model
+        with the ceps codebooks."""
+        p, a = self._pcm4(pcm, active)
+        pk = np.zeros((self.B, 8), np.uint8) if packets is None else packets
+        if pk.dtype != np.uint8 or pk.shape != (self.B, 8) or not pk.flags.c_contiguous:
+            raise ValueError(f"packets must be a contiguous uint8 [{self.B}, 8]")
+        f = self._out4(features) if want_features or features is not None else None
+        if lib.lpcnet_batch_encode(self._b, p.ctypes.data, pk.ctypes.data, None if f is None else f.ctypes.data,
+                                   None if a is None else a.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return pk, f
+
+    def compute_features4(self, pcm: np.ndarray, active: np.ndarray | None = None,
+                          out: np.ndarray | None = None) -> np.ndarray:
+        """lpcnet_compute_features (unquantised): pcm [B, 640] int16 ->
+        features [4, B, 36].  Needs no model."""
+        p, a = self._pcm4(pcm, active)
+        o = self._out4(out)
+        if lib.lpcnet_batch_compute_features4(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def encode_device(self, d_pcm: int, d_packets: int, d_features: int | None = None, row: int = NB_FEATURES,
+                      d_active: int | None = None, npackets: int = 1) -> None:
+        """Enqueue the encoder on device buffers: d_pcm [4 npackets, B, 160]
+        int16 (what synthesize_frames writes), d_packets [npackets, B, 8] (what
+        decode_frames reads), d_features [4 npackets, B, row] or None, row 20
+        or 36.  sync() waits."""
+        if lib.lpcnet_batch_encode_device(self._b, d_pcm, d_packets, d_features, row, d_active, npackets) != 0:
+            raise LPCNetError(last_error())
+
+    def encode_save_state(self, stream: int) -> bytes:
+        """The features snapshot followed by the encoder's vq_mem[18]."""
+        buf = C.create_string_buffer(lib.lpcnet_batch_encode_state_size(self._b))
+        if lib.lpcnet_batch_encode_save_state(self._b, stream, buf) != 0:
+            raise LPCNetError(last_error())
+        return buf.raw
+
+    def encode_restore_state(self, stream: int, state: bytes) -> None:
+        if len(state) != lib.lpcnet_batch_encode_state_size(self._b):
+            raise LPCNetError("encoder state of the wrong size")
+        if lib.lpcnet_batch_encode_restore_state(self._b, stream, state) != 0:
+            raise LPCNetError(last_error())
+
     # -- device-resident path (benchmarks) ---------------------------------
     def device_alloc(self, nbytes: int) -> int:
         p = lib.lpcnet_batch_device_alloc(self._b, nbytes)
@@ -737,7 +820,8 @@ class LPCNetBatch:
 
     def kernel_ms(self, which: int = 0) -> tuple[float, int]:
         """(total ms, launches) of the timed launches since reset_timers: which = 0 sample
-        kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor."""
+        kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor, 4 the 1.6 kb/s
+        encoder, 5 the part of 4 that is enc_kernel.hip."""
         n = C.c_int(0)
         ms = lib.lpcnet_batch_kernel_ms(self._b, which, C.byref(n))
         return ms, n.value

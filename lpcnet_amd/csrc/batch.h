@@ -34,6 +34,8 @@ using namespace lpcnet_mi355x;
     }                                                                                      \
   } while (0)
 
+constexpr int TIMED_REGIONS = 6; /* lpcnet_batch_kernel_ms's `which` */
+
 /* ------------------------------------------------------------------------ */
 struct LPCNetBatch {
   int device = 0;
@@ -135,13 +137,26 @@ struct LPCNetBatch {
   float *d_feat_pcm = nullptr;  /* [B][FRAME] float or short */
   float *d_feat_out = nullptr;  /* [B][NTF] */
   unsigned char *d_feat_act = nullptr;
+  /* 1.6 kb/s encoder (feat_kernel<true>, enc_kernel.hip), allocated by the
+   * first encode call (enc_ensure) in one buffer, d_enc_base: each stream's
+   * encoder vq_mem (state, beside d_feat_state; not the decoder's), the
+   * main_pitch table, the scratch of one packet and the host-I/O staging */
+  void *d_enc_base = nullptr;
+  float *d_enc_vq = nullptr;     /* [B][NBANDS] */
+  EncTables *d_enc_tab = nullptr;
+  float *d_enc_xc = nullptr, *d_enc_fw = nullptr, *d_enc_feat = nullptr, *d_enc_lpc = nullptr;
+  int *d_enc_fields = nullptr;
+  short *d_enc_pcm = nullptr;    /* [4][B][FRAME] */
+  unsigned char *d_enc_pk = nullptr; /* [B][8] */
+  float *d_enc_out = nullptr;    /* [4][B][NTF] */
   /* diagnostics */
   unsigned long long *d_stamps = nullptr;
   /* timing */
   int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
   std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
-  std::vector<hipEvent_t> ev_pairs[4]; /* sample kernel, frame kernel, PLC predictor, feature extractor */
-  std::vector<int> ev_frames[4];    /* frames covered by each pair */
+  /* sample kernel, frame kernel, PLC predictor, feature extractor, encoder, the encoder's enc_kernel part */
+  std::vector<hipEvent_t> ev_pairs[TIMED_REGIONS];
+  std::vector<int> ev_frames[TIMED_REGIONS];    /* frames covered by each pair */
   std::vector<hipEvent_t> ev_free;
   /* lower bound of every stream's frame_count (lpcnet.c:119) before the next
    * frame: the multi-frame sample launches start where no stream can still
@@ -168,7 +183,8 @@ bool gru_state_plausible(const float *v, size_t n);
 /* Timed regions (lpcnet_batch_kernel_ms; engine.cpp).  mark: with `on`, take
  * an event and record it on `s` (e = nullptr otherwise).  timed: the pair
  * (e0, e1) covers `frames` frames of region `which` (0 sample kernel, 1 frame
- * kernel, 2 PLC predictor, 3 feature extractor); a null event: no pair. */
+ * kernel, 2 PLC predictor, 3 feature extractor, 4 encoder, 5 the part of 4
+ * that is enc_kernel.hip); a null event: no pair. */
 int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e);
 void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames);
 

@@ -785,6 +785,7 @@ LPCNET_EXPORT int lpcnet_batch_reset_stream(LPCNetBatch *b, int stream)
   }
   /* and the analysis state (lpcnet_encoder_init inside lpcnet_plc_reset) */
   if (b->d_feat_state) HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
+  if (b->d_enc_vq) HIPCHK(hipMemsetAsync(b->d_enc_vq + (size_t)stream * NBANDS, 0, NBANDS * 4, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   b->min_fc = std::min(b->min_fc, s.frame_count);
   return 0;
@@ -799,6 +800,7 @@ LPCNET_EXPORT void lpcnet_batch_reset(LPCNetBatch *b)
   (void)hipMemcpyAsync(b->d_state, v.data(), sizeof(StreamState) * v.size(), hipMemcpyHostToDevice, b->stream);
   if (b->plc_ok) (void)hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * (b->pa.n1 + b->pa.n2) * 4, b->stream);
   if (b->d_feat_state) (void)hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream);
+  if (b->d_enc_vq) (void)hipMemsetAsync(b->d_enc_vq, 0, (size_t)b->B * NBANDS * 4, b->stream);
   (void)hipStreamSynchronize(b->stream);
   b->min_fc = v[0].frame_count;
 }
@@ -1309,7 +1311,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
   if (!b) return;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
-  for (int k = 0; k < 4; k++) {
+  for (int k = 0; k < TIMED_REGIONS; k++) {
     b->ev_pairs[k].clear();
     b->ev_frames[k].clear();
   }
@@ -1322,7 +1324,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
 
 LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *launches)
 {
-  if (!b || which < 0 || which > 3) return -1;
+  if (!b || which < 0 || which >= TIMED_REGIONS) return -1;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
   double tot = 0;
@@ -1337,7 +1339,7 @@ LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *laun
 
 LPCNET_EXPORT int lpcnet_batch_kernel_frames(LPCNetBatch *b, int which)
 {
-  if (!b || which < 0 || which > 3) return -1;
+  if (!b || which < 0 || which >= TIMED_REGIONS) return -1;
   int n = 0;
   for (int k : b->ev_frames[which]) n += k;
   return n;

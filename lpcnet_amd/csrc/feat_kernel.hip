@@ -18,6 +18,8 @@
  *                                       energy on one lane per half-frame
  *   3x interpolation         :553-570
  *   Viterbi + backtrack      :824-866   lane per state, strict > everywhere
+ * feat_kernel<true> is the same analysis for frame k of the 1.6 kb/s
+ * encoder's superframe, without process_single_frame (enc_kernel.hip).
  * Must be compiled with -ffp-contract=off.
  */
 #include <hip/hip_runtime.h>
@@ -63,6 +65,14 @@ __device__ __forceinline__ int fft_slot(int n)
 
 }  // namespace
 
+/* SUPER false: the single-frame extractor.  SUPER true: frame A.k of a
+ * superframe (lpcnet_encode / lpcnet_compute_features, lpcnet_enc.c:882-909):
+ * preemphasis and compute_frame_features with pcount = A.k, no
+ * process_single_frame; the frame's two xc rows (before the sub-harmonic
+ * check, which process_superframe runs) and frame_weights go to A.xc_out /
+ * A.fw_out, its cepstrum to A.features and its LPC to A.lpc_out, all scratch
+ * of the call that enc_kernel.hip consumes; the Viterbi state stays untouched. */
+template <bool SUPER>
 __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
 {
   __shared__ C2 ybuf[FS][WIN];
@@ -195,7 +205,11 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
   /* LPC residual (lpcnet_enc.c:527-537): pitch_mem[j] = aligned_in[i-1-j] */
   float s_last = 0.f;
   if (live) {
-    if (A.row == NTF && lane < NLPC) out[NF + lane] = sm[SM_LPC + lane];
+    if constexpr (SUPER) {
+      if (lane < NLPC) A.lpc_out[(size_t)sid * NLPC + lane] = sm[SM_LPC + lane];
+    } else {
+      if (A.row == NTF && lane < NLPC) out[NF + lane] = sm[SM_LPC + lane];
+    }
 #pragma unroll
     for (int t = 0; t < 3; t++) {
       const int i = lane + 64 * t;
@@ -288,9 +302,31 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
           nv[sub][t] = FMAX16(xc[sub][i], FMAX16(val1, val2));
         }
       }
-    /* pitch_max_path[0] into the FFT buffer (the ener values are consumed) */
-    for (int k = lane; k < PITCH_MAX; k += 64) yf[YF_ENER + k] = S->pitch_max_path[k];
+    if constexpr (SUPER) {
+      /* rows 2 + 2 k + sub of xc and frame_weight (lpcnet_enc.c:545-570) */
+#pragma unroll
+      for (int sub = 0; sub < 2; sub++) {
+        float *row = A.xc_out + ((size_t)sid * 8 + 2 * A.k + sub) * PITCH_MAX;
+#pragma unroll
+        for (int t = 0; t < 4; t++) row[lane + 64 * t] = nv[sub][t];
+      }
+      if (lane < 2) A.fw_out[(size_t)sid * 8 + 2 * A.k + lane] = sm[SM_IP + lane];
+      /* what crosses frames, but for the Viterbi state */
+#pragma unroll
+      for (int t = 0; t < 3; t++)
+        if (lane + 64 * t < FRAME) S->analysis_mem[lane + 64 * t] = in_r[t];
+      if (lane < NLPC) S->pitch_mem[NLPC - 1 - lane] = in_r[1];
+      for (int k = lane; k < PITCH_MAX; k += 64) S->exc[k] = exc[FRAME + k];
+      if (lane == (FRAME - 1) % 64) {
+        S->mem_preemph = -PREEMPH_COEF * x_last;
+        S->pitch_filt = s_last;
+      }
+    } else {
+      /* pitch_max_path[0] into the FFT buffer (the ener values are consumed) */
+      for (int k = lane; k < PITCH_MAX; k += 64) yf[YF_ENER + k] = S->pitch_max_path[k];
+    }
   }
+  if constexpr (SUPER) return; /* the whole workgroup: no barrier is left waiting */
   __syncthreads();
   if (live)
 #pragma unroll
@@ -423,7 +459,16 @@ int launch_feat(const FeatArgs &a, void *stream)
 {
   if (a.nstreams < 1 || (a.row != NF && a.row != NTF) || (!a.pcm && !a.pcm_f) || !a.features || !a.state) return -1;
   const int grid = (a.nstreams + FS - 1) / FS;
-  hipLaunchKernelGGL(feat_kernel, dim3(grid), dim3(64 * FS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(feat_kernel<false>, dim3(grid), dim3(64 * FS), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_feat_super(const FeatArgs &a, void *stream)
+{
+  if (a.nstreams < 1 || a.row != NF || !a.pcm || !a.features || !a.state || !a.xc_out || !a.fw_out || !a.lpc_out || a.k < 0 || a.k > 3)
+    return -1;
+  const int grid = (a.nstreams + FS - 1) / FS;
+  hipLaunchKernelGGL(feat_kernel<true>, dim3(grid), dim3(64 * FS), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

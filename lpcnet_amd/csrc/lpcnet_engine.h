@@ -499,8 +499,61 @@ struct FeatArgs {
   FeatState *state;            /* [B] */
   const LpcTables *lpc_tab;
   const FeatTables *tab;
+  /* the superframe form only (launch_feat_super): frame k of 4; features is
+   * then [B][NF] (row = NF) of that frame */
+  int k;
+  float *xc_out;               /* [B][8][PITCH_MAX]: rows 2 k, 2 k + 1 written */
+  float *fw_out;               /* [B][8] */
+  float *lpc_out;              /* [B][NLPC] of frame k */
 };
 int launch_feat(const FeatArgs &a, void *stream);
+int launch_feat_super(const FeatArgs &a, void *stream);
+
+/* lpcnet_encode / lpcnet_compute_features after their four frame analyses:
+ * process_superframe (lpcnet_enc.c:579-743) for a whole batch (enc_kernel.hip).
+ * The scratch below is written and consumed within one packet of one call and
+ * is no state; what crosses packets is FeatState (the Viterbi rows are the
+ * single-frame path's) and each stream's encoder vq_mem.
+ * Distances of 1e15f or more, and NaN, are outside the contract: the
+ * reference then reads uninitialised indices (lpcnet_enc.c:53-78, 138-147);
+ * here every index stays inside its codebook, and its value is unspecified.
+ * PCM input cannot produce such distances. */
+constexpr int ENC_PITCH_THR = 63; /* main_pitch = how many of these center_pitch reaches */
+struct EncTables {
+  float pitch_thr[ENC_PITCH_THR + 1]; /* ascending; [63] pads */
+};
+struct EncArgs {
+  int nstreams;
+  int quantize;                /* 1: lpcnet_encode (quantize = encode = 1); 0: lpcnet_compute_features */
+  const unsigned char *active; /* [B]; null: every stream */
+  FeatState *state;            /* [B] */
+  float *vq_mem;               /* [B][NBANDS], the encoder's (not the decoder's) */
+  float *xc;                   /* [B][8][PITCH_MAX] scratch: xc[2..9] */
+  float *fw;                   /* [B][8] scratch: frame_weight[2..9] */
+  float *feat;                 /* [4][B][NF] scratch: cepstra in, st->features[k][0..19] out */
+  int *fields;                 /* [B][4] scratch: c0_id + 64, main_pitch, modulation field, corr_id */
+  const float *lpc;            /* [4][B][NLPC] scratch (enc_out_kernel) */
+  const EncTables *tab;
+  const float *cb1, *cb2, *cb3, *cbd, *pitch; /* as DecodeArgs */
+  unsigned char *packets;      /* [B][8]; null: not written */
+  float *features;             /* [4][B][row]; null: not written */
+  int row;                     /* NF or NTF */
+};
+/* the Viterbi pass over xc[2..9], backtrack, pitch regression and quantisation, c0 */
+int launch_enc_pitch(const EncArgs &a, void *stream);
+/* quantize_3stage_mbest, quantize_diff, double_interp_search,
+ * perform_double_interp and bits_pack (quantize = 1 only) */
+int launch_enc_vq(const EncArgs &a, void *stream);
+/* live streams' rows of feat | lpc into features */
+int launch_enc_out(const EncArgs &a, void *stream);
+/* main_pitch of lpcnet_enc.c:678-679 from the threshold table, host and device alike */
+__host__ __device__ inline int enc_main_pitch(const float *thr, float cp)
+{
+  int m = 0;
+  if (cp < __builtin_inff()) /* inf: log = inf, floor, (int) = INT_MIN, IMIN, IMAX -> 0; NaN compares false */
+    for (int i = 0; i < ENC_PITCH_THR; i++) m += cp >= thr[i];
+  return m;
+}
 
 }  // namespace lpcnet_mi355x
 

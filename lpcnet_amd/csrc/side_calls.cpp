@@ -1,7 +1,8 @@
 /*
  * side_calls.cpp -- the device side of the calls beside synthesis: the PLC
  * prediction network (lpcnet_batch_plc_*), the feature extractor
- * (lpcnet_batch_*features*) and the stand-alone lpcnet_mi355x_device_lpc.
+ * (lpcnet_batch_*features*), the 1.6 kb/s encoder (lpcnet_batch_encode*) and
+ * the stand-alone lpcnet_mi355x_device_lpc.
  * Their tables are built host-only in side_tables.cpp; the batch they run on
  * and its timed regions are engine.cpp's (batch.h).  Argument errors are
  * reported before any device call.
@@ -88,6 +89,13 @@ void feat_free(LPCNetBatch *b)
   (void)hipFree(b->d_feat_pcm);
   (void)hipFree(b->d_feat_out);
   (void)hipFree(b->d_feat_act);
+  (void)hipFree(b->d_enc_base);
+  b->d_enc_base = nullptr;
+  b->d_enc_vq = b->d_enc_xc = b->d_enc_fw = b->d_enc_feat = b->d_enc_lpc = b->d_enc_out = nullptr;
+  b->d_enc_tab = nullptr;
+  b->d_enc_fields = nullptr;
+  b->d_enc_pcm = nullptr;
+  b->d_enc_pk = nullptr;
   b->d_feat_state = nullptr;
   b->d_feat_tab = nullptr;
   b->d_feat_pcm = b->d_feat_out = nullptr;
@@ -296,6 +304,10 @@ LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream)
   if (b->set_device()) return -1;
   if (stream < 0) HIPCHK(hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream));
   else HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
+  if (b->d_enc_vq) {
+    if (stream < 0) HIPCHK(hipMemsetAsync(b->d_enc_vq, 0, (size_t)b->B * NBANDS * 4, b->stream));
+    else HIPCHK(hipMemsetAsync(b->d_enc_vq + (size_t)stream * NBANDS, 0, NBANDS * 4, b->stream));
+  }
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -325,6 +337,216 @@ LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream
   if (b->set_device() || feat_ensure(b)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipMemcpy(b->d_feat_state + stream, &s, sizeof(s), hipMemcpyHostToDevice));
+  return 0;
+}
+
+}  // extern "C"
+
+/* ---- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) ------------- */
+
+/* the encoder's vq_mem, table, per-packet scratch and staging of a batch, on
+ * its first encode call: one zeroed buffer, every part 256-byte aligned */
+static int enc_ensure(LPCNetBatch *b)
+{
+  if (feat_ensure(b)) return -1;
+  if (b->d_enc_base) return 0;
+  const size_t B = (size_t)b->B;
+  size_t off = 0;
+  auto part = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_vq = part(B * NBANDS * 4), o_tab = part(sizeof(EncTables)), o_xc = part(B * 8 * PITCH_MAX * 4), o_fw = part(B * 8 * 4),
+               o_feat = part(4 * B * NF * 4), o_lpc = part(4 * B * NLPC * 4), o_fl = part(B * 4 * 4), o_pcm = part(4 * B * FRAME * 2),
+               o_pk = part(B * 8), o_out = part(4 * B * NTF * 4);
+  EncTables T;
+  build_enc_tables(T);
+  char *base = nullptr;
+  if (hipMalloc(&base, off) != hipSuccess || hipMemsetAsync(base, 0, off, b->stream) != hipSuccess ||
+      hipMemcpyAsync(base + o_tab, &T, sizeof(T), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
+      hipStreamSynchronize(b->stream) != hipSuccess) { /* T leaves scope */
+    (void)hipFree(base);
+    set_err("encode: device allocation failed");
+    return -1;
+  }
+  b->d_enc_base = base;
+  b->d_enc_vq = (float *)(base + o_vq);
+  b->d_enc_tab = (EncTables *)(base + o_tab);
+  b->d_enc_xc = (float *)(base + o_xc);
+  b->d_enc_fw = (float *)(base + o_fw);
+  b->d_enc_feat = (float *)(base + o_feat);
+  b->d_enc_lpc = (float *)(base + o_lpc);
+  b->d_enc_fields = (int *)(base + o_fl);
+  b->d_enc_pcm = (short *)(base + o_pcm);
+  b->d_enc_pk = (unsigned char *)(base + o_pk);
+  b->d_enc_out = (float *)(base + o_out);
+  return 0;
+}
+
+/* one packet on the batch's stream: d_pcm [4][B][FRAME]; d_packets [B][8] and
+ * d_features [4][B][row] may be null.  Timed as which = 4 (and the launches
+ * after the analysis as 5) when timing is on. */
+static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned char *d_packets, float *d_features, int row,
+                      const unsigned char *d_active)
+{
+  const size_t B = (size_t)b->B;
+  for (int k = 0; k < 4; k++) {
+    FeatArgs a{};
+    a.nstreams = b->B;
+    a.pcm = d_pcm + k * B * FRAME;
+    a.features = b->d_enc_feat + k * B * NF;
+    a.row = NF;
+    a.active = d_active;
+    a.state = b->d_feat_state;
+    a.lpc_tab = b->d_lpc_tab;
+    a.tab = b->d_feat_tab;
+    a.k = k;
+    a.xc_out = b->d_enc_xc;
+    a.fw_out = b->d_enc_fw;
+    a.lpc_out = b->d_enc_lpc + k * B * NLPC;
+    if (timed_launch(b, 4, b->timing != 0, 1, "encoder analysis kernel launch failed", [&] { return launch_feat_super(a, b->stream); }))
+      return -1;
+  }
+  EncArgs e{};
+  e.nstreams = b->B;
+  e.quantize = quantize;
+  e.active = d_active;
+  e.state = b->d_feat_state;
+  e.vq_mem = b->d_enc_vq;
+  e.xc = b->d_enc_xc;
+  e.fw = b->d_enc_fw;
+  e.feat = b->d_enc_feat;
+  e.fields = b->d_enc_fields;
+  e.lpc = b->d_enc_lpc;
+  e.tab = b->d_enc_tab;
+  if (quantize) {
+    e.cb1 = b->da.cb1;
+    e.cb2 = b->da.cb2;
+    e.cb3 = b->da.cb3;
+    e.cbd = b->da.cbd;
+    e.pitch = b->da.pitch;
+  }
+  e.packets = d_packets;
+  e.features = d_features;
+  e.row = row;
+  hipEvent_t e0, e1;
+  if (mark(b, b->timing != 0, b->stream, e0)) return -1;
+  if (launch_enc_pitch(e, b->stream)) { set_err("encoder pitch kernel launch failed"); return -1; }
+  if (quantize) {
+    if (launch_enc_vq(e, b->stream)) { set_err("encoder quantiser kernel launch failed"); return -1; }
+    /* lpc_from_cepstrum of the four quantised cepstra (lpcnet_enc.c:714-717);
+     * unquantised, the analysis has left the same LPC */
+    if (d_features && row == NTF && launch_lpc(b->d_enc_feat, b->d_enc_lpc, 4 * b->B, b->d_lpc_tab, b->stream)) {
+      set_err("encoder LPC kernel launch failed");
+      return -1;
+    }
+  }
+  if (d_features && launch_enc_out(e, b->stream)) { set_err("encoder output kernel launch failed"); return -1; }
+  if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
+  timed(b, 4, e0, e1, 0);
+  timed(b, 5, e0, e1, 4);
+  return 0;
+}
+
+static int enc_model_ready(const LPCNetBatch *b)
+{
+  if (!b->have_model) { set_err("lpcnet_encode: no model loaded (the quantiser needs its ceps codebooks)"); return -1; }
+  if (!b->has_codebooks) {
+    set_err("lpcnet_encode: the model blob carries no ceps_codebook1/2/3 / ceps_codebook_diff4 records");
+    return -1;
+  }
+  return 0;
+}
+
+static int enc_host(LPCNetBatch *b, const short *pcm, int quantize, unsigned char *packets, float *features,
+                    const unsigned char *active)
+{
+  if (!pcm || (quantize ? !packets : !features)) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (quantize && enc_model_ready(b)) return -1;
+  if (b->set_device() || enc_ensure(b)) return -1;
+  const size_t B = (size_t)b->B;
+  /* [B][640] -> [4][B][160] */
+  std::vector<short> t(4 * B * FRAME);
+  for (size_t s = 0; s < B; s++)
+    for (int k = 0; k < 4; k++) memcpy(&t[(k * B + s) * FRAME], pcm + s * 4 * FRAME + (size_t)k * FRAME, FRAME * 2);
+  HIPCHK(hipMemcpyAsync(b->d_enc_pcm, t.data(), t.size() * 2, hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
+  if (enc_packet(b, b->d_enc_pcm, quantize, quantize ? b->d_enc_pk : nullptr, features ? b->d_enc_out : nullptr, NTF,
+                 active ? b->d_feat_act : nullptr))
+    return -1;
+  if (quantize) {
+    std::vector<unsigned char> pk(B * 8);
+    HIPCHK(hipMemcpyAsync(pk.data(), b->d_enc_pk, pk.size(), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (size_t s = 0; s < B; s++)
+      if (!active || active[s]) memcpy(packets + s * 8, &pk[s * 8], 8);
+  }
+  if (features)
+    for (int k = 0; k < 4; k++)
+      if (copy_back_active(b, b->d_enc_out + k * B * NTF, NTF, features + k * B * NTF, active)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream)); /* t and the staging are free again */
+  return 0;
+}
+
+extern "C" {
+
+LPCNET_EXPORT int lpcnet_batch_encode(LPCNetBatch *b, const short *pcm, unsigned char *packets, float *features,
+                                      const unsigned char *active)
+{
+  return enc_host(b, pcm, 1, packets, features, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_compute_features4(LPCNetBatch *b, const short *pcm, float *features, const unsigned char *active)
+{
+  return enc_host(b, pcm, 0, nullptr, features, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_encode_device(LPCNetBatch *b, const short *d_pcm, unsigned char *d_packets, float *d_features,
+                                             int row, const unsigned char *d_active, int npackets)
+{
+  if (row != NF && row != NTF) { set_err("encode: row must be NB_FEATURES (20) or NB_TOTAL_FEATURES (36)"); return -1; }
+  if (npackets < 0) { set_err("encode: npackets < 0"); return -1; }
+  if (!d_pcm || !d_packets) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (enc_model_ready(b)) return -1;
+  if (b->set_device() || enc_ensure(b)) return -1;
+  const size_t B = (size_t)b->B;
+  /* the packets of a stream are sequential: one run of launches per packet */
+  for (int p = 0; p < npackets; p++)
+    if (enc_packet(b, d_pcm + p * 4 * B * FRAME, 1, d_packets + p * B * 8, d_features ? d_features + p * 4 * B * row : nullptr, row,
+                   d_active))
+      return -1;
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_encode_state_size(const LPCNetBatch *) { return (int)sizeof(FeatState) + NBANDS * 4; }
+
+LPCNET_EXPORT int lpcnet_batch_encode_save_state(LPCNetBatch *b, int stream, void *buf)
+{
+  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (stream >= b->B) { set_err("no such stream"); return -1; }
+  if (b->set_device() || enc_ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(buf, b->d_feat_state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy((char *)buf + sizeof(FeatState), b->d_enc_vq + (size_t)stream * NBANDS, NBANDS * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, const void *buf)
+{
+  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
+  FeatState s;
+  memcpy(&s, buf, sizeof(s));
+  if (s.best_i < 0 || s.best_i >= PITCH_STATES) { set_err("encoder snapshot: best_i outside [0, 224): not a state this engine produced"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (stream >= b->B) { set_err("no such stream"); return -1; }
+  if (b->set_device() || enc_ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(b->d_feat_state + stream, &s, sizeof(s), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->d_enc_vq + (size_t)stream * NBANDS, (const char *)buf + sizeof(FeatState), NBANDS * 4, hipMemcpyHostToDevice));
   return 0;
 }
 

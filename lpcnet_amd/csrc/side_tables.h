@@ -17,6 +17,8 @@ namespace lpcnet_mi355x {
 /* both memset their table first: padding is defined */
 void build_lpc_tables(LpcTables &T);
 void build_feat_tables(FeatTables &T);
+/* the encoder's main_pitch thresholds; a table of its own, in no digest */
+void build_enc_tables(EncTables &T);
 
 /* The records of training_tf2/dump_plc.py:121-250 under the rules of
  * dense_init, gru_init and find_idx_check (parse_lpcnet_weights.c:90-171);
