@@ -17,7 +17,7 @@ CSRC := lpcnet_amd/csrc
 HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/burg_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
@@ -90,6 +90,11 @@ $(BUILD)/plc_kernel.o: $(CSRC)/plc_kernel.hip $(HDRS) | $(BUILD)
 
 # the flags of lpc_kernel, whose stages it shares (lpc_stages.h)
 $(BUILD)/feat_kernel.o: $(CSRC)/feat_kernel.hip $(HDRS) | $(BUILD)
+	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+
+# burg_cepstral_analysis; feat_kernel's flags (one contracted a*b+c in the
+# recursion changes the output)
+$(BUILD)/burg_kernel.o: $(CSRC)/burg_kernel.hip $(HDRS) | $(BUILD)
 	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
 
 # process_superframe of the 1.6 kb/s encoder; feat_kernel's flags

@@ -205,8 +205,11 @@ LPCNET_EXPORT int lpcnet_batch_memcpy_d2h(LPCNetBatch *b, void *dst, const void 
  * 1.6 kb/s encoder (lpcnet_batch_encode*, lpcnet_batch_compute_features4:
  * the four analysis launches of a packet, one frame each, and the launches
  * of enc_kernel.hip as one region; likewise), 5 the part of 4 that is
- * enc_kernel.hip (four frames per region).  Returns total ms and the number
- * of launches.
+ * enc_kernel.hip (four frames per region), 6 the Burg analysis kernel
+ * (lpcnet_batch_burg_cepstrum*, _plc_rows_device with the Burg part,
+ * _plc_update*: one launch per frame, timed whenever enable > 0; the rows'
+ * extractor launch counts under 3, the update's predictor under 2).  Returns
+ * total ms and the number of launches.
  * enable: 0 off, 1 events around the sample kernel only, 2 (or more) around
  * both kernels. */
 LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable);
@@ -476,9 +479,10 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
  * of these calls: lpcnet_batch_state_size and the synthesis snapshots are
  * unchanged; lpcnet_batch_reset / _reset_stream zero it (lpcnet_encoder_init
  * inside lpcnet_plc_reset).
- * Out of scope: burg_cepstral_analysis, the PLC state machine,
- * process_multi_frame and drop-in LPCNetEncState handles (one stream per
- * launch is slower than the CPU).
+ * burg_cepstral_analysis and the predictor's input rows are the section
+ * "Burg cepstral analysis" below.
+ * Out of scope: the PLC state machine, process_multi_frame and drop-in
+ * LPCNetEncState handles (one stream per launch is slower than the CPU).
  * Argument errors return -1 with the reason in lpcnet_mi355x_last_error. */
 /* lpcnet_compute_single_frame_features for every stream s with active[s] != 0
  * (NULL: all). pcm [B][160]; features [B][NB_TOTAL_FEATURES]. Inactive streams:
@@ -499,6 +503,49 @@ LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream /* -1: 
 LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *b);
 LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf);
 LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf);
+
+/* ---- Burg cepstral analysis and the predictor's input rows -----------------
+ * burg_cepstral_analysis (freq.c:156-199, burg.c:98-245) for a whole batch in
+ * one launch per frame (burg_kernel.hip): 160 samples per stream -> 36 floats,
+ * the 18 half-sums and 18 differences of the two half-frames' Burg cepstra,
+ * bit-identical per stream to the reference's build (-ffp-contract=off, no
+ * fast-math).  It has no state across frames and no weights: these calls need
+ * no model, and no call that changes the model or its kernels changes their
+ * results.  Inputs on which the reference build aborts (the asserts of
+ * silk_burg_analysis: nrg_f > 0, nrg_b > 0, |rc| < 1) are outside the
+ * contract.
+ * With it every per-frame step of lpcnet_plc_update_causal / _non_causal
+ * (lpcnet_plc.c:205-258, 374-436) is a batch call: plc_rows assembles the
+ * predictor's input row [36 Burg cepstrum | 20 features | flag] in device
+ * memory, plc_update is rows + compute_plc_pred, the good-packet step.
+ * Out of scope: the PLC state machine itself (pcm_fill loops, blending, DC
+ * filter, FEC queue: per-stream host control flow over these batch calls),
+ * process_multi_frame and an fp32 predictor.
+ * Argument errors return -1 with the reason in lpcnet_mi355x_last_error and
+ * launch nothing. */
+/* burg_cepstral_analysis for every stream s with active[s] != 0 (NULL: all).
+ * pcm [B][160]; ceps [B][36]. Inactive streams: output row untouched. */
+LPCNET_EXPORT int lpcnet_batch_burg_cepstrum(LPCNetBatch *b, const short *pcm, float *ceps, const unsigned char *active);
+LPCNET_EXPORT int lpcnet_batch_burg_cepstrum_float(LPCNetBatch *b, const float *pcm, float *ceps, const unsigned char *active);
+/* device pointers, on the batch's stream: d_pcm [nframes][B][160] (what
+ * synthesize_frames writes); the 36 values go to d_out[(f*B + s)*row + col .. +36);
+ * row >= col + 36, col >= 0, anything else -1; other columns untouched. */
+LPCNET_EXPORT int lpcnet_batch_burg_cepstrum_device(LPCNetBatch *b, const short *d_pcm, float *d_out, int row, int col,
+                                                    const unsigned char *d_active, int nframes);
+
+#define LPCNET_PLC_ROW_BURG     1  /* columns 0..35 = burg_cepstral_analysis(d_pcm) */
+#define LPCNET_PLC_ROW_FEATURES 2  /* columns 36..55 = the extractor's first 20 features of d_pcm; advances the analysis state */
+/* One predictor input row [B][57] per active stream: the selected parts,
+ * zeros in an unselected part, `flag` in column 56 (lpcnet_plc.c:212-214,
+ * 256-257, 380-382, 434-435). d_pcm [B][160]. Inactive streams: row and state
+ * untouched. parts outside 1..3: -1. */
+LPCNET_EXPORT int lpcnet_batch_plc_rows_device(LPCNetBatch *b, const short *d_pcm, float *d_rows, int parts, float flag,
+                                               const unsigned char *d_active);
+/* The good-packet step: rows(BURG|FEATURES, flag 1) then compute_plc_pred;
+ * pcm / d_pcm [B][160], out / d_out [B][NB_FEATURES], neither NULL.  Needs a
+ * model with PLC records. */
+LPCNET_EXPORT int lpcnet_batch_plc_update(LPCNetBatch *b, const short *pcm, float *out, const unsigned char *active);
+LPCNET_EXPORT int lpcnet_batch_plc_update_device(LPCNetBatch *b, const short *d_pcm, float *d_out, const unsigned char *d_active);
 
 /* ---- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) -------------
  * lpcnet_enc.c:882-909 for a whole batch: four analysis launches

@@ -30,6 +30,9 @@ NB_FEATURES = 20
 NB_TOTAL_FEATURES = 36
 PLC_INPUTS = 57  # 2 NB_BANDS Burg cepstrum + NB_FEATURES + the loss flag (lpcnet_plc.c:149)
 FRAME_SIZE = 160
+BURG_CEPSTRUM = 36  # burg_cepstral_analysis: 18 half-sums and 18 differences of the half-frames' cepstra
+PLC_ROW_BURG = 1    # LPCNET_PLC_ROW_BURG
+PLC_ROW_FEATURES = 2  # LPCNET_PLC_ROW_FEATURES
 VARIANT_INT8 = 0
 VARIANT_FP32 = 1
 
@@ -139,6 +142,13 @@ def _load():
         "lpcnet_batch_features_state_size": (i, [vp]),
         "lpcnet_batch_features_save_state": (i, [vp, i, vp]),
         "lpcnet_batch_features_restore_state": (i, [vp, i, vp]),
+        # Burg cepstral analysis and the predictor's input rows
+        "lpcnet_batch_burg_cepstrum": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_burg_cepstrum_float": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_burg_cepstrum_device": (i, [vp, vp, vp, i, i, vp, i]),
+        "lpcnet_batch_plc_rows_device": (i, [vp, vp, vp, i, f, vp]),
+        "lpcnet_batch_plc_update": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_plc_update_device": (i, [vp, vp, vp, vp]),
         # 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features)
         "lpcnet_batch_encode": (i, [vp, vp, vp, vp, vp]),
         "lpcnet_batch_compute_features4": (i, [vp, vp, vp, vp]),
@@ -719,6 +729,70 @@ class LPCNetBatch:
         if lib.lpcnet_batch_features_restore_state(self._b, stream, state) != 0:
             raise LPCNetError(last_error())
 
+    # -- Burg cepstral analysis and the predictor's input rows ---------------
+    def burg_cepstrum(self, pcm: np.ndarray, active: np.ndarray | None = None,
+                      out: np.ndarray | None = None) -> np.ndarray:
+        """burg_cepstral_analysis on every stream with active[s] != 0 (None:
+        all).  pcm [B, 160], int16 or float32; returns [B, 36] -- rows of
+        inactive streams keep what ``out`` held (zeros without ``out``).
+        Needs no model and has no state."""
+        p = np.asarray(pcm)
+        if p.dtype not in (np.int16, np.float32):
+            raise ValueError("pcm must be int16 or float32")
+        p = np.ascontiguousarray(p)
+        if p.shape != (self.B, FRAME_SIZE):
+            raise ValueError(f"pcm must be [{self.B}, {FRAME_SIZE}]")
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        if a is not None and a.shape != (self.B,):
+            raise ValueError(f"active must be [{self.B}]")
+        o = np.zeros((self.B, BURG_CEPSTRUM), np.float32) if out is None else out
+        if o.dtype != np.float32 or o.shape != (self.B, BURG_CEPSTRUM) or not o.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous float32 [{self.B}, {BURG_CEPSTRUM}]")
+        fn = lib.lpcnet_batch_burg_cepstrum if p.dtype == np.int16 else lib.lpcnet_batch_burg_cepstrum_float
+        if fn(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def burg_cepstrum_device(self, d_pcm: int, d_out: int, row: int = BURG_CEPSTRUM, col: int = 0,
+                             d_active: int | None = None, nframes: int = 1) -> None:
+        """Enqueue the Burg analysis on device buffers: d_pcm [nframes, B, 160]
+        int16, the 36 values of frame f and stream s at
+        d_out[(f * B + s) * row + col]; row >= col + 36.  sync() waits."""
+        if lib.lpcnet_batch_burg_cepstrum_device(self._b, d_pcm, d_out, row, col, d_active, nframes) != 0:
+            raise LPCNetError(last_error())
+
+    def plc_rows_device(self, d_pcm: int, d_rows: int, parts: int = PLC_ROW_BURG | PLC_ROW_FEATURES, flag: float = 1.0,
+                        d_active: int | None = None) -> None:
+        """Enqueue the assembly of one predictor input row [B, 57] per active
+        stream from d_pcm [B, 160] int16: the Burg cepstrum (PLC_ROW_BURG),
+        the extractor's 20 features (PLC_ROW_FEATURES; advances the analysis
+        state), zeros in an unselected part, ``flag`` in column 56."""
+        if lib.lpcnet_batch_plc_rows_device(self._b, d_pcm, d_rows, parts, flag, d_active) != 0:
+            raise LPCNetError(last_error())
+
+    def plc_update(self, pcm: np.ndarray, active: np.ndarray | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """The PLC's good-packet step on every stream with active[s] != 0:
+        pcm [B, 160] int16 -> rows(Burg | features, flag 1) -> compute_plc_pred
+        -> [B, 20].  Rows of inactive streams keep what ``out`` held."""
+        p = np.ascontiguousarray(pcm)
+        if p.dtype != np.int16 or p.shape != (self.B, FRAME_SIZE):
+            raise ValueError(f"pcm must be int16 [{self.B}, {FRAME_SIZE}]")
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+        if a is not None and a.shape != (self.B,):
+            raise ValueError(f"active must be [{self.B}]")
+        o = np.zeros((self.B, NB_FEATURES), np.float32) if out is None else out
+        if o.dtype != np.float32 or o.shape != (self.B, NB_FEATURES) or not o.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous float32 [{self.B}, {NB_FEATURES}]")
+        if lib.lpcnet_batch_plc_update(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def plc_update_device(self, d_pcm: int, d_out: int, d_active: int | None = None) -> None:
+        """plc_update on device buffers: d_pcm [B, 160] int16, d_out [B, 20]
+        (what synthesize_frames reads as d_features).  sync() waits."""
+        if lib.lpcnet_batch_plc_update_device(self._b, d_pcm, d_out, d_active) != 0:
+            raise LPCNetError(last_error())
+
     # -- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) ----------
     def _pcm4(self, pcm: np.ndarray, active) -> tuple[np.ndarray, np.ndarray | None]:
         p = np.ascontiguousarray(pcm)
@@ -821,7 +895,7 @@ class LPCNetBatch:
     def kernel_ms(self, which: int = 0) -> tuple[float, int]:
         """(total ms, launches) of the timed launches since reset_timers: which = 0 sample
         kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor, 4 the 1.6 kb/s
-        encoder, 5 the part of 4 that is enc_kernel.hip."""
+        encoder, 5 the part of 4 that is enc_kernel.hip, 6 the Burg analysis."""
         n = C.c_int(0)
         ms = lib.lpcnet_batch_kernel_ms(self._b, which, C.byref(n))
         return ms, n.value

@@ -34,7 +34,7 @@ using namespace lpcnet_mi355x;
     }                                                                                      \
   } while (0)
 
-constexpr int TIMED_REGIONS = 6; /* lpcnet_batch_kernel_ms's `which` */
+constexpr int TIMED_REGIONS = 7; /* lpcnet_batch_kernel_ms's `which` */
 
 /* ------------------------------------------------------------------------ */
 struct LPCNetBatch {
@@ -137,6 +137,14 @@ struct LPCNetBatch {
   float *d_feat_pcm = nullptr;  /* [B][FRAME] float or short */
   float *d_feat_out = nullptr;  /* [B][NTF] */
   unsigned char *d_feat_act = nullptr;
+  /* Burg cepstral analysis (burg_kernel.hip): stateless; its table and the
+   * scratch of one call in one buffer (d_burg_tab is its start), allocated
+   * by the first call that runs it (burg_ensure); it shares the extractor's
+   * tables and host-I/O staging */
+  BurgTables *d_burg_tab = nullptr;
+  double *d_burg_c = nullptr;  /* [BURG_NC][2 B] */
+  float *d_burg_x = nullptr;   /* [2 NLPC][2 B] */
+  float *d_burg_o = nullptr;   /* [NLPC + 1][2 B] */
   /* 1.6 kb/s encoder (feat_kernel<true>, enc_kernel.hip), allocated by the
    * first encode call (enc_ensure) in one buffer, d_enc_base: each stream's
    * encoder vq_mem (state, beside d_feat_state; not the decoder's), the
@@ -154,7 +162,7 @@ struct LPCNetBatch {
   /* timing */
   int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
   std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
-  /* sample kernel, frame kernel, PLC predictor, feature extractor, encoder, the encoder's enc_kernel part */
+  /* sample kernel, frame kernel, PLC predictor, feature extractor, encoder, the encoder's enc_kernel part, Burg analysis */
   std::vector<hipEvent_t> ev_pairs[TIMED_REGIONS];
   std::vector<int> ev_frames[TIMED_REGIONS];    /* frames covered by each pair */
   std::vector<hipEvent_t> ev_free;
@@ -184,7 +192,7 @@ bool gru_state_plausible(const float *v, size_t n);
  * an event and record it on `s` (e = nullptr otherwise).  timed: the pair
  * (e0, e1) covers `frames` frames of region `which` (0 sample kernel, 1 frame
  * kernel, 2 PLC predictor, 3 feature extractor, 4 encoder, 5 the part of 4
- * that is enc_kernel.hip); a null event: no pair. */
+ * that is enc_kernel.hip, 6 Burg analysis); a null event: no pair. */
 int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e);
 void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames);
 

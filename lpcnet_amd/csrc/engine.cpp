@@ -286,7 +286,8 @@ int ensure_trace(LPCNetBatch *b, int N)
  * otherwise: with timing off there are no events at all).  The event belongs
  * to ev_taken from the moment it is taken, so a failing call leaks nothing.
  * timed: the pair (e0, e1) covers `frames` frames of region `which` (0 sample
- * kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor). */
+ * kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor, 4 and 5 the
+ * encoder, 6 the Burg analysis). */
 int lpcnet_mi355x::mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e)
 {
   e = nullptr;

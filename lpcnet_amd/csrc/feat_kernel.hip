@@ -113,7 +113,7 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
    * al[NLPC - 1 - j] = pitch_mem[j]; in xc's second row, which the
    * cross-correlation writes two barriers after the residual last read it */
   float *al = xcb[w][1];
-  float *out = A.features + (size_t)(live ? sid : 0) * A.row;
+  float *out = A.features + (size_t)(live ? sid : 0) * A.stride;
   __syncthreads(); /* the tables stand (the window below reads hwin) */
 
   /* preemphasis (lpcnet_enc.c:872-880: y = x + mem, mem = -coef x), the
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
 
 int launch_feat(const FeatArgs &a, void *stream)
 {
-  if (a.nstreams < 1 || (a.row != NF && a.row != NTF) || (!a.pcm && !a.pcm_f) || !a.features || !a.state) return -1;
+  if (a.nstreams < 1 || (a.row != NF && a.row != NTF) || a.stride < a.row || (!a.pcm && !a.pcm_f) || !a.features || !a.state) return -1;
   const int grid = (a.nstreams + FS - 1) / FS;
   hipLaunchKernelGGL(feat_kernel<false>, dim3(grid), dim3(64 * FS), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -465,7 +465,7 @@ int launch_feat(const FeatArgs &a, void *stream)
 
 int launch_feat_super(const FeatArgs &a, void *stream)
 {
-  if (a.nstreams < 1 || a.row != NF || !a.pcm || !a.features || !a.state || !a.xc_out || !a.fw_out || !a.lpc_out || a.k < 0 || a.k > 3)
+  if (a.nstreams < 1 || a.row != NF || a.stride != NF || !a.pcm || !a.features || !a.state || !a.xc_out || !a.fw_out || !a.lpc_out || a.k < 0 || a.k > 3)
     return -1;
   const int grid = (a.nstreams + FS - 1) / FS;
   hipLaunchKernelGGL(feat_kernel<true>, dim3(grid), dim3(64 * FS), 0, (hipStream_t)stream, a);

@@ -493,8 +493,9 @@ struct FeatArgs {
   int nstreams;
   const short *pcm;            /* [B][FRAME], or */
   const float *pcm_f;          /* [B][FRAME] when pcm is null */
-  float *features;             /* [B][row] */
+  float *features;             /* stream s writes features[s * stride .. + row) */
   int row;                     /* NF or NTF */
+  int stride;                  /* floats between two streams' rows, >= row (row: a dense [B][row]) */
   const unsigned char *active; /* [B]; null: every stream */
   FeatState *state;            /* [B] */
   const LpcTables *lpc_tab;
@@ -508,6 +509,41 @@ struct FeatArgs {
 };
 int launch_feat(const FeatArgs &a, void *stream);
 int launch_feat_super(const FeatArgs &a, void *stream);
+
+/* burg_cepstral_analysis (freq.c:156-199, burg.c:98-245) for a whole batch
+ * (burg_kernel.hip): 160 samples per stream -> 18 sums and 18 differences of
+ * the two half-frames' Burg cepstra.  No state, no weights.  The table is a
+ * struct of its own, uploaded on first use, in no digest. */
+constexpr int BURG_N = 2 * NBANDS;          /* floats per stream */
+constexpr int BURG_LEN = FRAME / 2 - 1;     /* burg_in samples of a half-frame (len - 1) */
+constexpr int BURG_NC = NLPC + 2;           /* C0, lags 1..16, the energy of the first 16 samples */
+struct BurgTables {
+  double pw[NLPC]; /* pow(.995, i + 1) (freq.c:174), the host's */
+};
+constexpr int BURG_FILL_ZERO = 1; /* +0.f into out[BURG_N .. BURG_N + NF) */
+constexpr int BURG_FILL_FLAG = 2; /* flag into out[PLC_IN - 1] */
+struct BurgArgs {
+  int nstreams;
+  const short *pcm;            /* [B][FRAME], or */
+  const float *pcm_f;          /* [B][FRAME] when pcm is null */
+  float *out;                  /* stream s writes out[s * stride .. + BURG_N) */
+  int stride;                  /* >= BURG_N; >= PLC_IN with a fill */
+  int fill;                    /* BURG_FILL_*: the rest of a predictor input row that starts at out */
+  float flag;
+  const unsigned char *active; /* [B]; null: every stream */
+  const LpcTables *lpc_tab;
+  const FeatTables *tab;
+  const BurgTables *btab;
+  /* scratch of one call, column 2 s + h of 2 B: the autocorrelations, the
+   * recursion's 32 samples, then the filter input and the gain */
+  double *cbuf;                /* [BURG_NC][2 B] */
+  float *xbuf;                 /* [2 NLPC][2 B] */
+  float *obuf;                 /* [NLPC + 1][2 B] */
+};
+int launch_burg(const BurgArgs &a, void *stream);
+/* a predictor input row without its Burg part: +0.f into rows[s][0 .. BURG_N),
+ * flag into rows[s][PLC_IN - 1] of every live stream; rows [B][PLC_IN] */
+int launch_plc_row_fill(float *rows, float flag, const unsigned char *active, int nstreams, void *stream);
 
 /* lpcnet_encode / lpcnet_compute_features after their four frame analyses:
  * process_superframe (lpcnet_enc.c:579-743) for a whole batch (enc_kernel.hip).

@@ -1,8 +1,10 @@
 /*
  * side_calls.cpp -- the device side of the calls beside synthesis: the PLC
  * prediction network (lpcnet_batch_plc_*), the feature extractor
- * (lpcnet_batch_*features*), the 1.6 kb/s encoder (lpcnet_batch_encode*) and
- * the stand-alone lpcnet_mi355x_device_lpc.
+ * (lpcnet_batch_*features*), the Burg analysis, the predictor's input rows
+ * and the good-packet step (lpcnet_batch_burg_cepstrum*, _plc_rows_device,
+ * _plc_update*), the 1.6 kb/s encoder (lpcnet_batch_encode*) and the
+ * stand-alone lpcnet_mi355x_device_lpc.
  * Their tables are built host-only in side_tables.cpp; the batch they run on
  * and its timed regions are engine.cpp's (batch.h).  Argument errors are
  * reported before any device call.
@@ -90,6 +92,10 @@ void feat_free(LPCNetBatch *b)
   (void)hipFree(b->d_feat_out);
   (void)hipFree(b->d_feat_act);
   (void)hipFree(b->d_enc_base);
+  (void)hipFree(b->d_burg_tab);
+  b->d_burg_tab = nullptr;
+  b->d_burg_c = nullptr;
+  b->d_burg_x = b->d_burg_o = nullptr;
   b->d_enc_base = nullptr;
   b->d_enc_vq = b->d_enc_xc = b->d_enc_fw = b->d_enc_feat = b->d_enc_lpc = b->d_enc_out = nullptr;
   b->d_enc_tab = nullptr;
@@ -239,7 +245,7 @@ static int feat_ensure(LPCNetBatch *b)
 
 /* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
 static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
-                       const unsigned char *d_active)
+                       const unsigned char *d_active, int stride = 0)
 {
   FeatArgs a{};
   a.nstreams = b->B;
@@ -247,6 +253,7 @@ static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f,
   a.pcm_f = d_pcm_f;
   a.features = d_features;
   a.row = row;
+  a.stride = stride ? stride : row; /* the dense [B][row] of every call but the predictor rows */
   a.active = d_active;
   a.state = b->d_feat_state;
   a.lpc_tab = b->d_lpc_tab;
@@ -342,6 +349,157 @@ LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream
 
 }  // extern "C"
 
+/* ---- Burg cepstral analysis, the predictor's input rows (burg_kernel.hip) --- */
+
+static_assert(BURG_N == NTF, "the Burg calls stage their output in d_feat_out");
+
+/* the extractor's tables and staging, and in one buffer the Burg table and
+ * the scratch its three stages hand over through, on a batch's first Burg call */
+static int burg_ensure(LPCNetBatch *b)
+{
+  if (feat_ensure(b)) return -1;
+  if (b->d_burg_tab) return 0;
+  const size_t n2 = 2 * (size_t)b->B;
+  size_t off = 0;
+  auto part = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_tab = part(sizeof(BurgTables)), o_c = part(BURG_NC * n2 * 8), o_x = part(2 * NLPC * n2 * 4), o_o = part((NLPC + 1) * n2 * 4);
+  BurgTables T;
+  build_burg_tables(T);
+  char *base = nullptr;
+  if (hipMalloc(&base, off) != hipSuccess || hipMemcpy(base + o_tab, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(base);
+    set_err("burg: device allocation failed");
+    return -1;
+  }
+  b->d_burg_tab = (BurgTables *)(base + o_tab); /* the buffer's start: feat_free frees it */
+  b->d_burg_c = (double *)(base + o_c);
+  b->d_burg_x = (float *)(base + o_x);
+  b->d_burg_o = (float *)(base + o_o);
+  return 0;
+}
+
+/* one Burg analysis (its three launches) on the batch's stream, timed as one region, which = 6, when timing is on */
+static int burg_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_out, int stride, int fill, float flag,
+                       const unsigned char *d_active)
+{
+  BurgArgs a{};
+  a.nstreams = b->B;
+  a.pcm = d_pcm;
+  a.pcm_f = d_pcm_f;
+  a.out = d_out;
+  a.stride = stride;
+  a.fill = fill;
+  a.flag = flag;
+  a.active = d_active;
+  a.lpc_tab = b->d_lpc_tab;
+  a.tab = b->d_feat_tab;
+  a.btab = b->d_burg_tab;
+  a.cbuf = b->d_burg_c;
+  a.xbuf = b->d_burg_x;
+  a.obuf = b->d_burg_o;
+  return timed_launch(b, 6, b->timing != 0, 1, "Burg kernel launch failed", [&] { return launch_burg(a, b->stream); });
+}
+
+static int burg_host(LPCNetBatch *b, const void *pcm, bool is_float, float *ceps, const unsigned char *active)
+{
+  if (!pcm || !ceps) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (b->set_device() || burg_ensure(b)) return -1;
+  const size_t B = (size_t)b->B;
+  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * (is_float ? 4 : 2), hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
+  if (burg_launch(b, is_float ? nullptr : (const short *)b->d_feat_pcm, is_float ? b->d_feat_pcm : nullptr, b->d_feat_out, BURG_N, 0, 0.f,
+                  active ? b->d_feat_act : nullptr))
+    return -1;
+  return copy_back_active(b, b->d_feat_out, BURG_N, ceps, active);
+}
+
+/* one predictor input row per live stream on the batch's stream, no host
+ * round trip: the Burg kernel writes its 36 values, the flag and, without the
+ * extractor, the zeros of columns 36..55; the extractor writes its 20 values
+ * at column 36 of the 57-wide rows; without the Burg part a fill kernel
+ * writes the zeros of columns 0..35 and the flag */
+static int plc_rows(LPCNetBatch *b, const short *d_pcm, float *d_rows, int parts, float flag, const unsigned char *d_active)
+{
+  if (parts & LPCNET_PLC_ROW_BURG) {
+    const int fill = BURG_FILL_FLAG | ((parts & LPCNET_PLC_ROW_FEATURES) ? 0 : BURG_FILL_ZERO);
+    if (burg_launch(b, d_pcm, nullptr, d_rows, PLC_IN, fill, flag, d_active)) return -1;
+  } else if (launch_plc_row_fill(d_rows, flag, d_active, b->B, b->stream)) {
+    set_err("predictor row fill kernel launch failed");
+    return -1;
+  }
+  if ((parts & LPCNET_PLC_ROW_FEATURES) && feat_launch(b, d_pcm, nullptr, d_rows + BURG_N, NF, d_active, PLC_IN)) return -1;
+  return 0;
+}
+
+extern "C" {
+
+LPCNET_EXPORT int lpcnet_batch_burg_cepstrum(LPCNetBatch *b, const short *pcm, float *ceps, const unsigned char *active)
+{
+  return burg_host(b, pcm, false, ceps, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_burg_cepstrum_float(LPCNetBatch *b, const float *pcm, float *ceps, const unsigned char *active)
+{
+  return burg_host(b, pcm, true, ceps, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_burg_cepstrum_device(LPCNetBatch *b, const short *d_pcm, float *d_out, int row, int col,
+                                                    const unsigned char *d_active, int nframes)
+{
+  if (col < 0) { set_err("burg: col < 0"); return -1; }
+  if (row < col + BURG_N) { set_err("burg: row must be at least col + 36"); return -1; }
+  if (nframes < 0) { set_err("burg: nframes < 0"); return -1; }
+  if (!d_pcm || !d_out) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (b->set_device() || burg_ensure(b)) return -1;
+  for (int f = 0; f < nframes; f++)
+    if (burg_launch(b, d_pcm + (size_t)f * b->B * FRAME, nullptr, d_out + (size_t)f * b->B * row + col, row, 0, 0.f, d_active)) return -1;
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_rows_device(LPCNetBatch *b, const short *d_pcm, float *d_rows, int parts, float flag,
+                                               const unsigned char *d_active)
+{
+  if (parts < 1 || parts > (LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES)) {
+    set_err("plc rows: parts must be LPCNET_PLC_ROW_BURG, LPCNET_PLC_ROW_FEATURES or both");
+    return -1;
+  }
+  if (!d_pcm || !d_rows) { set_err("bad arguments"); return -1; }
+  if (!b) { set_err("null batch"); return -1; }
+  if (b->set_device() || burg_ensure(b)) return -1;
+  return plc_rows(b, d_pcm, d_rows, parts, flag, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_update_device(LPCNetBatch *b, const short *d_pcm, float *d_out, const unsigned char *d_active)
+{
+  if (plc_ready(b)) return -1;
+  if (!d_pcm || !d_out) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || burg_ensure(b)) return -1;
+  if (plc_rows(b, d_pcm, b->d_plc_in, LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES, 1.f, d_active)) return -1;
+  return plc_launch(b, b->d_plc_in, d_out, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_plc_update(LPCNetBatch *b, const short *pcm, float *out, const unsigned char *active)
+{
+  if (plc_ready(b)) return -1;
+  if (!pcm || !out) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || burg_ensure(b)) return -1;
+  const size_t B = (size_t)b->B;
+  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * 2, hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
+  const unsigned char *d_act = active ? b->d_feat_act : nullptr;
+  if (plc_rows(b, (const short *)b->d_feat_pcm, b->d_plc_in, LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES, 1.f, d_act)) return -1;
+  if (plc_launch(b, b->d_plc_in, b->d_plc_out, d_act)) return -1;
+  return copy_back_active(b, b->d_plc_out, NF, out, active);
+}
+
+}  // extern "C"
+
 /* ---- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) ------------- */
 
 /* the encoder's vq_mem, table, per-packet scratch and staging of a batch, on
@@ -397,6 +555,7 @@ static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned
     a.pcm = d_pcm + k * B * FRAME;
     a.features = b->d_enc_feat + k * B * NF;
     a.row = NF;
+    a.stride = NF;
     a.active = d_active;
     a.state = b->d_feat_state;
     a.lpc_tab = b->d_lpc_tab;

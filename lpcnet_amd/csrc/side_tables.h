@@ -1,7 +1,8 @@
 /*
  * side_tables.h -- the host-built tables of what runs beside synthesis: the
- * constants of lpc_from_cepstrum (lpc_kernel.hip) and of the feature
- * extractor (feat_kernel.hip), and the PLC prediction network's records
+ * constants of lpc_from_cepstrum (lpc_kernel.hip), of the feature extractor
+ * (feat_kernel.hip) and of the Burg analysis (burg_kernel.hip), and the PLC
+ * prediction network's records
  * re-tiled for plc_kernel.hip.  No device call: side_calls.cpp uploads them,
  * tools/model_host_check.cpp decodes the PLC tiles on the CPU.
  */
@@ -19,6 +20,8 @@ void build_lpc_tables(LpcTables &T);
 void build_feat_tables(FeatTables &T);
 /* the encoder's main_pitch thresholds; a table of its own, in no digest */
 void build_enc_tables(EncTables &T);
+/* the Burg analysis' pow(.995, i + 1) doubles; a table of its own, in no digest */
+void build_burg_tables(BurgTables &T);
 
 /* The records of training_tf2/dump_plc.py:121-250 under the rules of
  * dense_init, gru_init and find_idx_check (parse_lpcnet_weights.c:90-171);
