@@ -2,8 +2,9 @@
 #
 #   make            -> lpcnet_amd/liblpcnet_mi355x.so + oracle/ libraries
 #   make lib        -> the product library only
-#   make check      -> builds and runs tools/model_host_check and
-#                      tools/pool_combiner_check (CPU only)
+#   make check      -> builds and runs tools/model_host_check,
+#                      tools/pool_combiner_check and tools/feat_host_check
+#                      (CPU only)
 #
 # Every translation unit is compiled with -ffp-contract=off: the engine is
 # bit-exact with the reference x86 build only without FMA contraction.
@@ -42,78 +43,27 @@ $(DROPIN): tools/dropin_bench.c include/lpcnet.h include/lpcnet_mi355x.h $(LIB)
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/kernels.o: $(CSRC)/kernels.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+# The objects hipcc compiles, all with one command line: the kernels (.hip),
+# the batch API (engine.cpp), the drop-in single-stream API over it
+# (dropin.cpp), the PLC, feature, Burg, encoder and LPC calls beside synthesis
+# (side_calls.cpp) and the host-only GRU_A planner, blob -> HostModel ingest
+# and side tables (mf_plan, model_host, side_tables).  feat_kernel, burg_kernel
+# and enc_kernel share lpc_kernel's stages (lpc_stages.h) and so
+# its flags: one contracted a*b+c in the Burg recursion changes the output.
+# XFLAGS: what single objects add, below.
+HIPCC_O = $(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) $(XFLAGS) -c $< -o $@
 
-$(BUILD)/frame_kernel.o: $(CSRC)/frame_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+$(BUILD)/%.o: $(CSRC)/%.hip $(HDRS) | $(BUILD)
+	$(HIPCC_O)
+
+$(BUILD)/%.o: $(CSRC)/%.cpp $(HDRS) | $(BUILD)
+	$(HIPCC_O)
 
 # no SLP vectorisation: packed f32 ops cost the shared SIMDs more than scalar pairs
-$(BUILD)/mf_kernel.o: $(CSRC)/mf_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -fno-slp-vectorize -c $< -o $@
-
-$(BUILD)/mf2_kernel.o: $(CSRC)/mf2_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -fno-slp-vectorize -c $< -o $@
-
-$(BUILD)/mfw_kernel.o: $(CSRC)/mfw_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -fno-slp-vectorize -c $< -o $@
+$(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/mfw_kernel.o: XFLAGS := -fno-slp-vectorize
 
 # the fp32 chains schedule better under the max-ILP machine scheduler (batch-1 fp32 +0.6 %)
-$(BUILD)/fp_kernel.o: $(CSRC)/fp_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -mllvm -amdgpu-sched-strategy=max-ilp -c $< -o $@
-
-$(BUILD)/selftest.o: $(CSRC)/selftest.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/engine.o: $(CSRC)/engine.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-# the drop-in single-stream API over the batch engine (batch.h)
-$(BUILD)/dropin.o: $(CSRC)/dropin.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-# the PLC, feature and LPC calls beside synthesis, on the engine's batch (batch.h)
-$(BUILD)/side_calls.o: $(CSRC)/side_calls.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/lpc_kernel.o: $(CSRC)/lpc_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/chunk_kernel.o: $(CSRC)/chunk_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/decode_kernel.o: $(CSRC)/decode_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/plc_kernel.o: $(CSRC)/plc_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-# the flags of lpc_kernel, whose stages it shares (lpc_stages.h)
-$(BUILD)/feat_kernel.o: $(CSRC)/feat_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-# burg_cepstral_analysis; feat_kernel's flags (one contracted a*b+c in the
-# recursion changes the output)
-$(BUILD)/burg_kernel.o: $(CSRC)/burg_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-# process_superframe of the 1.6 kb/s encoder; feat_kernel's flags
-$(BUILD)/enc_kernel.o: $(CSRC)/enc_kernel.hip $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/model_gen.o: $(CSRC)/model_gen.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-# host-only code: the GRU_A planner, the blob -> HostModel ingest and the
-# tables beside the synthesis model (PLC predictor, LPC, feature extractor)
-$(BUILD)/mf_plan.o: $(CSRC)/mf_plan.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/model_host.o: $(CSRC)/model_host.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
-
-$(BUILD)/side_tables.o: $(CSRC)/side_tables.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+$(BUILD)/fp_kernel.o: XFLAGS := -mllvm -amdgpu-sched-strategy=max-ilp
 
 # host-only: the CPU's own rcpps (x86 SSE), system compiler
 $(BUILD)/host_rcpps.o: $(CSRC)/host_rcpps.cpp include/lpcnet_mi355x.h | $(BUILD)
@@ -137,7 +87,7 @@ $(LIB): $(OBJS)
 HOSTCHECK := tools/model_host_check
 
 $(BUILD)/model_host_check.o: tools/model_host_check.cpp $(HDRS) | $(BUILD)
-	$(HIPCC) -x hip --offload-arch=$(ARCH) $(COMMON) -c $< -o $@
+	$(HIPCC_O)
 
 $(HOSTCHECK): $(BUILD)/model_host_check.o $(BUILD)/model_host.o $(BUILD)/side_tables.o $(BUILD)/mf_plan.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
@@ -149,17 +99,26 @@ POOLCHECK := tools/pool_combiner_check
 $(POOLCHECK): tools/pool_combiner_check.cpp $(BUILD)/pool_combiner.o $(CSRC)/pool_combiner.h
 	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $< $(BUILD)/pool_combiner.o -lpthread
 
-hostcheck: $(HOSTCHECK) $(POOLCHECK)
+# stand-alone check of what the side calls answer without a device, plain C
+# against the public header and the in-tree library
+# (tools/feat_host_check.c gives the sanitizer recipe)
+FEATCHECK := tools/feat_host_check
 
-check: $(HOSTCHECK) $(POOLCHECK)
+$(FEATCHECK): tools/feat_host_check.c include/lpcnet_mi355x.h $(LIB)
+	$(CC) -std=c99 -O2 -Wall -Wextra -Werror -Iinclude -o $@ $< -Llpcnet_amd -llpcnet_mi355x -Wl,-rpath,'$$ORIGIN/../lpcnet_amd'
+
+hostcheck: $(HOSTCHECK) $(POOLCHECK) $(FEATCHECK)
+
+check: hostcheck
 	$(HOSTCHECK)
 	$(POOLCHECK)
+	$(FEATCHECK)
 
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK)
+	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK) $(FEATCHECK)
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib synth dropin hostcheck oracle clean check

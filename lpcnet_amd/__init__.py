@@ -455,6 +455,57 @@ class _BatchOwner:
             self.ptr = None
 
 
+def _pcm_arg(pcm, shape: tuple[int, int], float_ok: bool = False) -> np.ndarray:
+    """The caller's PCM as a contiguous array of ``shape``: int16, or with
+    float_ok float32 as well (the reference's short -> float conversion done)."""
+    p = np.ascontiguousarray(pcm)
+    if float_ok:
+        if p.dtype not in (np.int16, np.float32):
+            raise ValueError("pcm must be int16 or float32")
+        if p.shape != shape:
+            raise ValueError(f"pcm must be [{shape[0]}, {shape[1]}]")
+    elif p.dtype != np.int16 or p.shape != shape:
+        raise ValueError(f"pcm must be int16 [{shape[0]}, {shape[1]}]")
+    return p
+
+
+def _active_arg(active, B: int) -> np.ndarray | None:
+    """The active mask as B bytes (None: every stream)."""
+    a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+    if a is not None and a.shape != (B,):
+        raise ValueError(f"active must be [{B}]")
+    return a
+
+
+def _out_arg(out, shape: tuple, dtype=np.float32, what: str = "out") -> np.ndarray:
+    """The caller's ``out``, used in place (rows of inactive streams keep their
+    content), or zeros without one."""
+    o = np.zeros(shape, dtype) if out is None else out
+    if o.dtype != dtype or o.shape != shape or not o.flags.c_contiguous:
+        raise ValueError(f"{what} must be a contiguous {np.dtype(dtype).name} [{', '.join(map(str, shape))}]")
+    return o
+
+
+def _ptr(a: np.ndarray | None):
+    return None if a is None else a.ctypes.data
+
+
+def _save_snapshot(save, b, stream: int, size: int) -> bytes:
+    if size < 0:
+        raise LPCNetError(last_error())
+    buf = C.create_string_buffer(size)
+    if save(b, stream, buf) != 0:
+        raise LPCNetError(last_error())
+    return buf.raw
+
+
+def _restore_snapshot(restore, b, stream: int, state: bytes, size: int, wrong_size: str) -> None:
+    if len(state) != size:
+        raise LPCNetError(wrong_size)
+    if restore(b, stream, state) != 0:
+        raise LPCNetError(last_error())
+
+
 def _owned_view(owner: _BatchOwner, addr: int, ctype, dtype, shape) -> np.ndarray:
     n = int(np.prod(shape))
     buf = (ctype * n).from_address(addr)
@@ -610,10 +661,7 @@ class LPCNetBatch:
             raise LPCNetError(last_error())
 
     def save_state(self, stream: int) -> bytes:
-        buf = C.create_string_buffer(lib.lpcnet_batch_state_size())
-        if lib.lpcnet_batch_save_state(self._b, stream, buf) != 0:
-            raise LPCNetError(last_error())
-        return buf.raw
+        return _save_snapshot(lib.lpcnet_batch_save_state, self._b, stream, lib.lpcnet_batch_state_size())
 
     def restore_state(self, stream: int, state: bytes) -> None:
         if lib.lpcnet_batch_restore_state(self._b, stream, state) != 0:
@@ -636,17 +684,9 @@ class LPCNetBatch:
         x = None if inputs is None else np.ascontiguousarray(inputs, np.float32)
         if x is not None and x.shape != (self.B, PLC_INPUTS):
             raise ValueError(f"inputs must be [{self.B}, {PLC_INPUTS}]")
-        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        if a is not None and a.shape != (self.B,):
-            raise ValueError(f"active must be [{self.B}]")
-        o = None
-        if not discard:
-            o = np.zeros((self.B, NB_FEATURES), np.float32) if out is None else out
-            if o.dtype != np.float32 or o.shape != (self.B, NB_FEATURES) or not o.flags.c_contiguous:
-                raise ValueError(f"out must be a contiguous float32 [{self.B}, {NB_FEATURES}]")
-        if lib.lpcnet_batch_plc_predict(self._b, None if x is None else x.ctypes.data,
-                                        None if o is None else o.ctypes.data,
-                                        None if a is None else a.ctypes.data) != 0:
+        a = _active_arg(active, self.B)
+        o = None if discard else _out_arg(out, (self.B, NB_FEATURES))
+        if lib.lpcnet_batch_plc_predict(self._b, _ptr(x), _ptr(o), _ptr(a)) != 0:
             raise LPCNetError(last_error())
         return o
 
@@ -664,19 +704,11 @@ class LPCNetBatch:
 
     def plc_save_state(self, stream: int) -> bytes:
         """plc_gru1_state | plc_gru2_state of one stream (the PLC's PLCNetState copies)."""
-        n = lib.lpcnet_batch_plc_state_size(self._b)
-        if n < 0:
-            raise LPCNetError(last_error())
-        buf = C.create_string_buffer(n)
-        if lib.lpcnet_batch_plc_save_state(self._b, stream, buf) != 0:
-            raise LPCNetError(last_error())
-        return buf.raw
+        return _save_snapshot(lib.lpcnet_batch_plc_save_state, self._b, stream, lib.lpcnet_batch_plc_state_size(self._b))
 
     def plc_restore_state(self, stream: int, state: bytes) -> None:
-        if len(state) != lib.lpcnet_batch_plc_state_size(self._b):
-            raise LPCNetError(last_error() or "PLC state of the wrong size")
-        if lib.lpcnet_batch_plc_restore_state(self._b, stream, state) != 0:
-            raise LPCNetError(last_error())
+        _restore_snapshot(lib.lpcnet_batch_plc_restore_state, self._b, stream, state, lib.lpcnet_batch_plc_state_size(self._b),
+                          last_error() or "PLC state of the wrong size")  # the size call's error, when it left one
 
     # -- feature extraction (lpcnet_compute_single_frame_features) ----------
     def compute_features(self, pcm: np.ndarray, active: np.ndarray | None = None,
@@ -686,20 +718,11 @@ class LPCNetBatch:
         (the reference's short -> float conversion already done); returns
         [B, 36] features -- rows of inactive streams keep what ``out`` held
         (zeros without ``out``).  Needs no model."""
-        p = np.asarray(pcm)
-        if p.dtype not in (np.int16, np.float32):
-            raise ValueError("pcm must be int16 or float32")
-        p = np.ascontiguousarray(p)
-        if p.shape != (self.B, FRAME_SIZE):
-            raise ValueError(f"pcm must be [{self.B}, {FRAME_SIZE}]")
-        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        if a is not None and a.shape != (self.B,):
-            raise ValueError(f"active must be [{self.B}]")
-        o = np.zeros((self.B, NB_TOTAL_FEATURES), np.float32) if out is None else out
-        if o.dtype != np.float32 or o.shape != (self.B, NB_TOTAL_FEATURES) or not o.flags.c_contiguous:
-            raise ValueError(f"out must be a contiguous float32 [{self.B}, {NB_TOTAL_FEATURES}]")
+        p = _pcm_arg(pcm, (self.B, FRAME_SIZE), float_ok=True)
+        a = _active_arg(active, self.B)
+        o = _out_arg(out, (self.B, NB_TOTAL_FEATURES))
         fn = lib.lpcnet_batch_compute_features if p.dtype == np.int16 else lib.lpcnet_batch_compute_features_float
-        if fn(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+        if fn(self._b, _ptr(p), _ptr(o), _ptr(a)) != 0:
             raise LPCNetError(last_error())
         return o
 
@@ -718,16 +741,11 @@ class LPCNetBatch:
             raise LPCNetError(last_error())
 
     def features_save_state(self, stream: int) -> bytes:
-        buf = C.create_string_buffer(lib.lpcnet_batch_features_state_size(self._b))
-        if lib.lpcnet_batch_features_save_state(self._b, stream, buf) != 0:
-            raise LPCNetError(last_error())
-        return buf.raw
+        return _save_snapshot(lib.lpcnet_batch_features_save_state, self._b, stream, lib.lpcnet_batch_features_state_size(self._b))
 
     def features_restore_state(self, stream: int, state: bytes) -> None:
-        if len(state) != lib.lpcnet_batch_features_state_size(self._b):
-            raise LPCNetError("analysis state of the wrong size")
-        if lib.lpcnet_batch_features_restore_state(self._b, stream, state) != 0:
-            raise LPCNetError(last_error())
+        _restore_snapshot(lib.lpcnet_batch_features_restore_state, self._b, stream, state,
+                          lib.lpcnet_batch_features_state_size(self._b), "analysis state of the wrong size")
 
     # -- Burg cepstral analysis and the predictor's input rows ---------------
     def burg_cepstrum(self, pcm: np.ndarray, active: np.ndarray | None = None,
@@ -736,20 +754,11 @@ class LPCNetBatch:
         all).  pcm [B, 160], int16 or float32; returns [B, 36] -- rows of
         inactive streams keep what ``out`` held (zeros without ``out``).
         Needs no model and has no state."""
-        p = np.asarray(pcm)
-        if p.dtype not in (np.int16, np.float32):
-            raise ValueError("pcm must be int16 or float32")
-        p = np.ascontiguousarray(p)
-        if p.shape != (self.B, FRAME_SIZE):
-            raise ValueError(f"pcm must be [{self.B}, {FRAME_SIZE}]")
-        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        if a is not None and a.shape != (self.B,):
-            raise ValueError(f"active must be [{self.B}]")
-        o = np.zeros((self.B, BURG_CEPSTRUM), np.float32) if out is None else out
-        if o.dtype != np.float32 or o.shape != (self.B, BURG_CEPSTRUM) or not o.flags.c_contiguous:
-            raise ValueError(f"out must be a contiguous float32 [{self.B}, {BURG_CEPSTRUM}]")
+        p = _pcm_arg(pcm, (self.B, FRAME_SIZE), float_ok=True)
+        a = _active_arg(active, self.B)
+        o = _out_arg(out, (self.B, BURG_CEPSTRUM))
         fn = lib.lpcnet_batch_burg_cepstrum if p.dtype == np.int16 else lib.lpcnet_batch_burg_cepstrum_float
-        if fn(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+        if fn(self._b, _ptr(p), _ptr(o), _ptr(a)) != 0:
             raise LPCNetError(last_error())
         return o
 
@@ -774,16 +783,10 @@ class LPCNetBatch:
         """The PLC's good-packet step on every stream with active[s] != 0:
         pcm [B, 160] int16 -> rows(Burg | features, flag 1) -> compute_plc_pred
         -> [B, 20].  Rows of inactive streams keep what ``out`` held."""
-        p = np.ascontiguousarray(pcm)
-        if p.dtype != np.int16 or p.shape != (self.B, FRAME_SIZE):
-            raise ValueError(f"pcm must be int16 [{self.B}, {FRAME_SIZE}]")
-        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        if a is not None and a.shape != (self.B,):
-            raise ValueError(f"active must be [{self.B}]")
-        o = np.zeros((self.B, NB_FEATURES), np.float32) if out is None else out
-        if o.dtype != np.float32 or o.shape != (self.B, NB_FEATURES) or not o.flags.c_contiguous:
-            raise ValueError(f"out must be a contiguous float32 [{self.B}, {NB_FEATURES}]")
-        if lib.lpcnet_batch_plc_update(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+        p = _pcm_arg(pcm, (self.B, FRAME_SIZE))
+        a = _active_arg(active, self.B)
+        o = _out_arg(out, (self.B, NB_FEATURES))
+        if lib.lpcnet_batch_plc_update(self._b, _ptr(p), _ptr(o), _ptr(a)) != 0:
             raise LPCNetError(last_error())
         return o
 
@@ -794,21 +797,6 @@ class LPCNetBatch:
             raise LPCNetError(last_error())
 
     # -- 1.6 kb/s encoder (lpcnet_encode, lpcnet_compute_features) ----------
-    def _pcm4(self, pcm: np.ndarray, active) -> tuple[np.ndarray, np.ndarray | None]:
-        p = np.ascontiguousarray(pcm)
-        if p.dtype != np.int16 or p.shape != (self.B, 4 * FRAME_SIZE):
-            raise ValueError(f"pcm must be int16 [{self.B}, {4 * FRAME_SIZE}]")
-        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
-        if a is not None and a.shape != (self.B,):
-            raise ValueError(f"active must be [{self.B}]")
-        return p, a
-
-    def _out4(self, out: np.ndarray | None) -> np.ndarray:
-        o = np.zeros((4, self.B, NB_TOTAL_FEATURES), np.float32) if out is None else out
-        if o.dtype != np.float32 or o.shape != (4, self.B, NB_TOTAL_FEATURES) or not o.flags.c_contiguous:
-            raise ValueError(f"features must be a contiguous float32 [4, {self.B}, {NB_TOTAL_FEATURES}]")
-        return o
-
     def encode(self, pcm: np.ndarray, active: np.ndarray | None = None, packets: np.ndarray | None = None,
                features: np.ndarray | None = None, want_features: bool = True):
         """lpcnet_encode on every stream with active[s] != 0 (None: all): pcm
@@ -816,13 +804,13 @@ class LPCNetBatch:
         st->features after quantisation.  Rows of inactive streams keep what
         ``packets`` / ``features`` held (zeros without them).  Needs a model
         with the ceps codebooks."""
-        p, a = self._pcm4(pcm, active)
-        pk = np.zeros((self.B, 8), np.uint8) if packets is None else packets
-        if pk.dtype != np.uint8 or pk.shape != (self.B, 8) or not pk.flags.c_contiguous:
-            raise ValueError(f"packets must be a contiguous uint8 [{self.B}, 8]")
-        f = self._out4(features) if want_features or features is not None else None
-        if lib.lpcnet_batch_encode(self._b, p.ctypes.data, pk.ctypes.data, None if f is None else f.ctypes.data,
-                                   None if a is None else a.ctypes.data) != 0:
+        p = _pcm_arg(pcm, (self.B, 4 * FRAME_SIZE))
+        a = _active_arg(active, self.B)
+        pk = _out_arg(packets, (self.B, 8), np.uint8, "packets")
+        f = None
+        if want_features or features is not None:
+            f = _out_arg(features, (4, self.B, NB_TOTAL_FEATURES), what="features")
+        if lib.lpcnet_batch_encode(self._b, _ptr(p), _ptr(pk), _ptr(f), _ptr(a)) != 0:
             raise LPCNetError(last_error())
         return pk, f
 
@@ -830,9 +818,10 @@ class LPCNetBatch:
                           out: np.ndarray | None = None) -> np.ndarray:
         """lpcnet_compute_features (unquantised): pcm [B, 640] int16 ->
         features [4, B, 36].  Needs no model."""
-        p, a = self._pcm4(pcm, active)
-        o = self._out4(out)
-        if lib.lpcnet_batch_compute_features4(self._b, p.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data) != 0:
+        p = _pcm_arg(pcm, (self.B, 4 * FRAME_SIZE))
+        a = _active_arg(active, self.B)
+        o = _out_arg(out, (4, self.B, NB_TOTAL_FEATURES), what="features")
+        if lib.lpcnet_batch_compute_features4(self._b, _ptr(p), _ptr(o), _ptr(a)) != 0:
             raise LPCNetError(last_error())
         return o
 
@@ -847,16 +836,11 @@ class LPCNetBatch:
 
     def encode_save_state(self, stream: int) -> bytes:
         """The features snapshot followed by the encoder's vq_mem[18]."""
-        buf = C.create_string_buffer(lib.lpcnet_batch_encode_state_size(self._b))
-        if lib.lpcnet_batch_encode_save_state(self._b, stream, buf) != 0:
-            raise LPCNetError(last_error())
-        return buf.raw
+        return _save_snapshot(lib.lpcnet_batch_encode_save_state, self._b, stream, lib.lpcnet_batch_encode_state_size(self._b))
 
     def encode_restore_state(self, stream: int, state: bytes) -> None:
-        if len(state) != lib.lpcnet_batch_encode_state_size(self._b):
-            raise LPCNetError("encoder state of the wrong size")
-        if lib.lpcnet_batch_encode_restore_state(self._b, stream, state) != 0:
-            raise LPCNetError(last_error())
+        _restore_snapshot(lib.lpcnet_batch_encode_restore_state, self._b, stream, state,
+                          lib.lpcnet_batch_encode_state_size(self._b), "encoder state of the wrong size")
 
     # -- device-resident path (benchmarks) ---------------------------------
     def device_alloc(self, nbytes: int) -> int:

@@ -36,6 +36,56 @@ using namespace lpcnet_mi355x;
 
 constexpr int TIMED_REGIONS = 7; /* lpcnet_batch_kernel_ms's `which` */
 
+/* The device buffers of the calls beside synthesis (side_calls.cpp), one
+ * value-initialised group per family: freeing a group is hipFree of what it
+ * owns and `= {}`.
+ * PLC prediction network (plc_kernel.hip): each stream's plc_gru1_state |
+ * plc_gru2_state outside StreamState (the synthesis snapshots keep their
+ * size) and the host-I/O staging; they and the tables are LPCNetBatch's
+ * plc_bufs, buffers of their own (a re-plan of the synthesis tables keeps
+ * them). */
+struct PlcBufs {
+  float *state = nullptr;
+  float *in = nullptr, *out = nullptr; /* [B][PLC_IN], [B][NF] */
+  unsigned char *act = nullptr;
+};
+/* feature extractor (feat_kernel.hip): no weights, so nothing here depends
+ * on the model; each stream's analysis state, the constant tables and the
+ * host-I/O staging, one buffer (base) allocated by the first call that
+ * extracts features (feat_ensure) */
+struct FeatBufs {
+  void *base = nullptr;
+  FeatState *state = nullptr;
+  FeatTables *tab = nullptr;
+  float *pcm = nullptr; /* [B][FRAME] float or short */
+  float *out = nullptr; /* [B][NTF] */
+  unsigned char *act = nullptr;
+};
+/* Burg cepstral analysis (burg_kernel.hip): stateless; its table and the
+ * scratch of one call in one buffer, allocated by the first call that runs
+ * it (burg_ensure); it shares the extractor's tables and host-I/O staging */
+struct BurgBufs {
+  void *base = nullptr;
+  BurgTables *tab = nullptr;
+  double *c = nullptr; /* [BURG_NC][2 B] */
+  float *x = nullptr;  /* [2 NLPC][2 B] */
+  float *o = nullptr;  /* [NLPC + 1][2 B] */
+};
+/* 1.6 kb/s encoder (feat_kernel<true>, enc_kernel.hip), allocated by the
+ * first encode call (enc_ensure) in one buffer: each stream's encoder vq_mem
+ * (state, beside the extractor's; not the decoder's), the main_pitch table,
+ * the scratch of one packet and the host-I/O staging */
+struct EncBufs {
+  void *base = nullptr;
+  float *vq = nullptr; /* [B][NBANDS] */
+  EncTables *tab = nullptr;
+  float *xc = nullptr, *fw = nullptr, *feat = nullptr, *lpc = nullptr;
+  int *fields = nullptr;
+  short *pcm = nullptr;        /* [4][B][FRAME] */
+  unsigned char *pk = nullptr; /* [B][8] */
+  float *out = nullptr;        /* [4][B][NTF] */
+};
+
 /* ------------------------------------------------------------------------ */
 struct LPCNetBatch {
   int device = 0;
@@ -117,46 +167,16 @@ struct LPCNetBatch {
   unsigned char *d_packets = nullptr;
   float *d_dfeat = nullptr;
   short *d_dpcm = nullptr;
-  /* PLC prediction network (plc_kernel.hip): optional blob records, tables in
-   * buffers of their own (a re-plan of the synthesis tables keeps them), each
-   * stream's plc_gru1_state | plc_gru2_state outside StreamState (the
-   * synthesis snapshots keep their size), host-I/O staging */
+  /* PLC prediction network: optional blob records */
   bool plc_ok = false;
   std::string plc_why = "no model loaded"; /* why the PLC calls refuse this batch */
   PlcArgs pa{};
   std::vector<void *> plc_bufs;
-  float *d_plc_state = nullptr;
-  float *d_plc_in = nullptr, *d_plc_out = nullptr;
-  unsigned char *d_plc_act = nullptr;
-  /* feature extractor (feat_kernel.hip): no weights, so nothing here depends
-   * on the model; each stream's analysis state in an array of its own, the
-   * constant tables and the host-I/O staging, all allocated by the first
-   * call that extracts features (feat_ensure) */
-  FeatState *d_feat_state = nullptr;
-  FeatTables *d_feat_tab = nullptr;
-  float *d_feat_pcm = nullptr;  /* [B][FRAME] float or short */
-  float *d_feat_out = nullptr;  /* [B][NTF] */
-  unsigned char *d_feat_act = nullptr;
-  /* Burg cepstral analysis (burg_kernel.hip): stateless; its table and the
-   * scratch of one call in one buffer (d_burg_tab is its start), allocated
-   * by the first call that runs it (burg_ensure); it shares the extractor's
-   * tables and host-I/O staging */
-  BurgTables *d_burg_tab = nullptr;
-  double *d_burg_c = nullptr;  /* [BURG_NC][2 B] */
-  float *d_burg_x = nullptr;   /* [2 NLPC][2 B] */
-  float *d_burg_o = nullptr;   /* [NLPC + 1][2 B] */
-  /* 1.6 kb/s encoder (feat_kernel<true>, enc_kernel.hip), allocated by the
-   * first encode call (enc_ensure) in one buffer, d_enc_base: each stream's
-   * encoder vq_mem (state, beside d_feat_state; not the decoder's), the
-   * main_pitch table, the scratch of one packet and the host-I/O staging */
-  void *d_enc_base = nullptr;
-  float *d_enc_vq = nullptr;     /* [B][NBANDS] */
-  EncTables *d_enc_tab = nullptr;
-  float *d_enc_xc = nullptr, *d_enc_fw = nullptr, *d_enc_feat = nullptr, *d_enc_lpc = nullptr;
-  int *d_enc_fields = nullptr;
-  short *d_enc_pcm = nullptr;    /* [4][B][FRAME] */
-  unsigned char *d_enc_pk = nullptr; /* [B][8] */
-  float *d_enc_out = nullptr;    /* [4][B][NTF] */
+  /* the buffers of the calls beside synthesis */
+  PlcBufs plc{};
+  FeatBufs feat{};
+  BurgBufs burg{};
+  EncBufs enc{};
   /* diagnostics */
   unsigned long long *d_stamps = nullptr;
   /* timing */
@@ -230,6 +250,12 @@ int decode_first(LPCNetBatch *b, int nB, const unsigned char *packets, short *pc
 void plc_load(LPCNetBatch *b, const std::vector<Arr> &L);
 void plc_free(LPCNetBatch *b);
 void feat_free(LPCNetBatch *b);
+/* side_reset: queue on b->stream the zeroing of the side state the batch
+ * holds, of one stream or of all (stream < 0): the predictor's GRU states
+ * (SIDE_PLC), the analysis state and the encoder's vq_mem (SIDE_FEAT).  The
+ * caller synchronises. */
+enum { SIDE_PLC = 1, SIDE_FEAT = 2 };
+int side_reset(LPCNetBatch *b, int stream, int parts);
 
 }  // namespace lpcnet_mi355x
 

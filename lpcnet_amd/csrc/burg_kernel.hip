@@ -26,9 +26,8 @@
  *   residual energy, A       burg.c:219-244        both forms
  *   gain, filter input       freq.c:171-174        float division; the pow
  *                                                  values are the host's
- *   forward_transform        freq.c:242-254        lpc_stages.h, the slots
- *                                                  and scale of feat_kernel,
- *                                                  full butterflies
+ *   forward_transform        freq.c:242-254        lpc_stages.h: fft_slot and
+ *                                                  the scale, full butterflies
  *   compute_band_energy_inverse  freq.c:60-84      lane per band, serial walk
  *   scaling, log10, follower freq.c:177-183        double log10; the 2.5 of
  *                                                  the follower is a double
@@ -56,18 +55,7 @@ constexpr int HALF = FRAME / 2;
 constexpr int L = BURG_LEN;           /* subfr_length of silk_burg_analysis */
 constexpr int D = NLPC;               /* its order */
 constexpr int NC = BURG_NC;           /* C0, lags 1..16, the energy of the first D samples */
-constexpr float PREEMPH_COEF = 0.85f; /* freq.h:34 PREEMPHASIS */
 constexpr float COND_FAC = 1e-5f;     /* burg.c:40 FIND_LPC_COND_FAC, a float literal */
-
-#define BMAX16(a, b) ((a) > (b) ? (a) : (b)) /* arch.h:73 */
-
-/* as feat_kernel.hip: sample n = d0 + 5 d1 + 20 d2 + 80 d3 feeds FFT slot
- * 64 d0 + 16 d1 + 4 d2 + d3 */
-__device__ __forceinline__ int fft_slot(int n)
-{
-  const int d3 = n / 80, r = n % 80, d2 = r / 20, r2 = r % 20, d1 = r2 / 5, d0 = r2 % 5;
-  return 64 * d0 + 16 * d1 + 4 * d2 + d3;
-}
 
 /* silk_energy_FLP / silk_inner_product_FLP (burg.c:43-94): double products,
  * result += ((p0 + p1) + p2) + p3, then the remainder one by one */
@@ -265,10 +253,8 @@ __global__ __launch_bounds__(64 * BS) void burg_ceps_kernel(BurgArgs A)
   const int sid = blockIdx.x * BS + w;
   const bool live = sid < A.nstreams && (!A.active || A.active[sid]); /* wave-uniform */
   const LpcTables *T = A.lpc_tab;
-  for (int k = threadIdx.x; k < WIN; k += blockDim.x) tw[k] = C2{T->twr[k], T->twi[k]};
-  for (int k = threadIdx.x; k < NBANDS * NBANDS; k += blockDim.x) dct[k] = T->dct[k];
-  for (int k = threadIdx.x; k < FRAME; k += blockDim.x) frac[k] = A.tab->frac[k];
-  if (threadIdx.x < NBANDS) bstart[threadIdx.x] = A.tab->band_start[threadIdx.x];
+  stage_fft_dct<false>(T, tw, dct, nullptr);
+  stage_bands<false>(A.tab, frac, bstart, nullptr);
   const double sq = T->sqrt_2_18;
   const float scale = T->scale;
   float *out = A.out + (size_t)(live ? sid : 0) * A.stride;
@@ -293,26 +279,11 @@ __global__ __launch_bounds__(64 * BS) void burg_ceps_kernel(BurgArgs A)
   fft320_stages(live, lane, ybuf[w][0], tw);
   fft320_stages(live, lane, ybuf[w][1], tw);
 
-  /* compute_band_energy_inverse (freq.c:60-84), the walk of feat_kernel's
-   * lpcn_compute_band_energy; the scaling of :177 and the log10 of :179 */
+  /* compute_band_energy_inverse (freq.c:60-84), lpc_stages.h's walk over
+   * 1/(|y|^2 + 1e-9), a double sum and quotient rounded to float; the scaling
+   * of :177 and the log10 of :179 */
   if (live && l < NBANDS) {
-    const C2 *y = ybuf[w][h];
-    float sum = 0;
-    if (l > 0)
-      for (int k = bstart[l - 1]; k < bstart[l]; k++) {
-        float tmp = y[k].r * y[k].r;
-        tmp += y[k].i * y[k].i;
-        tmp = (float)(1.f / (tmp + 1e-9));
-        sum += frac[k] * tmp;
-      }
-    if (l < NBANDS - 1)
-      for (int k = bstart[l]; k < bstart[l + 1]; k++) {
-        float tmp = y[k].r * y[k].r;
-        tmp += y[k].i * y[k].i;
-        tmp = (float)(1.f / (tmp + 1e-9));
-        sum += (1 - frac[k]) * tmp;
-      }
-    if (l == 0 || l == NBANDS - 1) sum *= 2;
+    float sum = band_energy_walk(l, ybuf[w][h], frac, bstart, [](float p) { return (float)(1.f / (p + 1e-9)); });
     sum = (float)(sum * (.45 * gs[w][h] * (1.f / ((float)WIN * WIN * WIN))));
     lyb[w][h][l] = (float)log10(1e-2 + sum);
   }
@@ -325,9 +296,9 @@ __global__ __launch_bounds__(64 * BS) void burg_ceps_kernel(BurgArgs A)
 #pragma unroll
     for (int i = 0; i < NBANDS; i++) {
       float ly = lyb[w][h][i];
-      ly = (float)BMAX16(logMax - 8, BMAX16(follow - 2.5, ly));
-      logMax = BMAX16(logMax, ly);
-      follow = (float)BMAX16(follow - 2.5, ly);
+      ly = (float)MAX16(logMax - 8, MAX16(follow - 2.5, ly));
+      logMax = MAX16(logMax, ly);
+      follow = (float)MAX16(follow - 2.5, ly);
       acc += ly * dct[i * NBANDS + l];
     }
     float c = (float)(acc * sq);

@@ -35,6 +35,7 @@
 
 #include "device_math.h"
 #include "lpcnet_engine.h"
+#include "lpc_stages.h"
 
 namespace lpcnet_mi355x {
 
@@ -62,9 +63,6 @@ constexpr int DSTRIDE = NBANDS + 1;   /* LDS row stride of the difference codebo
 constexpr int CB_LDS = CB_N * NB1 > DQ_N * DSTRIDE ? CB_N * NB1 : DQ_N * DSTRIDE;
 constexpr int SURV = 5;               /* SURVIVORS */
 constexpr int FORBIDDEN = 7;          /* lpcnet_private.h:23 FORBIDDEN_INTERP */
-
-#define FMAX16(a, b) ((a) > (b) ? (a) : (b)) /* arch.h:73 */
-#define FMIN16(a, b) ((a) < (b) ? (a) : (b)) /* arch.h:72 */
 
 }  // namespace
 
@@ -101,19 +99,10 @@ __global__ __launch_bounds__(64 * PS) void enc_pitch_kernel(EncArgs A)
     for (int k = lane; k < PITCH_MAX; k += 64) pmp[k] = S->pitch_max_path[k];
   }
   __syncthreads();
-  /* the sub-harmonic check (:607-610) reads entries above i only: every read
-   * before any write (feat_kernel.hip) */
+  /* the sub-harmonic check (:607-610): every read before any write (lpc_stages.h) */
   for (int sub = 0; sub < 8; sub++) {
     float nv[3];
-    if (live)
-#pragma unroll
-      for (int t = 0; t < 3; t++) {
-        const int i = lane + 64 * t;
-        const float *r = xc[sub];
-        const float xc_half = FMAX16(FMAX16(r[(PITCH_MAX + i) / 2], r[(PITCH_MAX + i + 2) / 2]), r[(PITCH_MAX + i - 1) / 2]);
-        nv[t] = r[i];
-        if (r[i] < xc_half * 1.1f) nv[t] = r[i] * .8f;
-      }
+    if (live) subharmonic_row(xc[sub], lane, nv);
     __syncthreads();
     if (live)
 #pragma unroll
@@ -124,56 +113,7 @@ __global__ __launch_bounds__(64 * PS) void enc_pitch_kernel(EncArgs A)
   /* the forward pass (:604-635), as feat_kernel's over two rows */
   float max_all = live ? S->pitch_max_path_all : 0.f;
   int best_i = live ? S->best_i : 0;
-  for (int sub = 0; sub < 8; sub++) {
-    float pv[4] = {0.f, 0.f, 0.f, 0.f};
-    float cur = -1e15f;
-    int cur_i = 0;
-    if (live) {
-#pragma unroll
-      for (int t = 0; t < 4; t++) {
-        const int i = lane + 64 * t;
-        if (i < NST) {
-          float max_prev = max_all - 6.f;
-          int pp = best_i;
-#pragma unroll
-          for (int j = -4; j <= 4; j++)
-            if (j >= -i && i + j < NST) {
-              const int aj = j < 0 ? -j : j;
-              const float v = pmp[i + j] - .02f * aj * aj;
-              if (v > max_prev) {
-                max_prev = v;
-                pp = i + j;
-              }
-            }
-          prevb[w][sub][i] = (unsigned char)pp;
-          pv[t] = max_prev + fw[sub] * xc[sub][i];
-          if (pv[t] > cur) {
-            cur = pv[t];
-            cur_i = i;
-          }
-        }
-      }
-      /* the first index of the maximum, as the serial strict > keeps it */
-#pragma unroll
-      for (int m = 1; m < 64; m <<= 1) {
-        const float ov = __shfl_xor(cur, m, 64);
-        const int oi = __shfl_xor(cur_i, m, 64);
-        if (ov > cur || (ov == cur && oi < cur_i)) {
-          cur = ov;
-          cur_i = oi;
-        }
-      }
-    }
-    __syncthreads();
-    if (live) {
-#pragma unroll
-      for (int t = 0; t < 4; t++)
-        if (lane + 64 * t < NST) pmp[lane + 64 * t] = pv[t] - cur;
-      max_all = cur;
-      best_i = cur_i;
-    }
-    __syncthreads();
-  }
+  for (int sub = 0; sub < 8; sub++) viterbi_step(live, lane, pmp, xc[sub], fw[sub], prevb[w][sub], max_all, best_i);
   if (!live) return; /* no barrier below */
 
   for (int k = lane; k < NST; k += 64) S->pitch_max_path[k] = pmp[k];
@@ -223,8 +163,8 @@ __global__ __launch_bounds__(64 * PS) void enc_pitch_kernel(EncArgs A)
   if (voiced) {
     const float mean_pitch = sy / sw;
     const float max_a = mean_pitch / 32;
-    const float lo = FMAX16(-max_a, best_a);
-    best_a = FMIN16(max_a, lo);
+    const float lo = MAX16(-max_a, best_a);
+    best_a = MIN16(max_a, lo);
     corr_id = cvtt_f64(floor((double)((frame_corr - .3f) / .175f)));
     frame_corr = 0.3875f + .175f * corr_id;
   } else {
@@ -242,8 +182,8 @@ __global__ __launch_bounds__(64 * PS) void enc_pitch_kernel(EncArgs A)
   for (int sub = 0; sub < 4; sub++) {
     float p = A.pitch[main_pitch]; /* (float)(pow(2.f, main_pitch/21.)*PITCH_MIN_PERIOD) */
     p *= 1.f + modulation / 16.f / 7.f * (2 * sub - 3);
-    const float lo = FMAX16(33, p);
-    p = FMIN16(255, lo);
+    const float lo = MAX16(33, p);
+    p = MIN16(255, lo);
     feat[sub * fs + NBANDS] = .02f * (p - 100);
     feat[sub * fs + NBANDS + 1] = frame_corr - .5f;
   }

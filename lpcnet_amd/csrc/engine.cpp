@@ -779,14 +779,9 @@ LPCNET_EXPORT int lpcnet_batch_reset_stream(LPCNetBatch *b, int stream)
   StreamState s;
   host_reset_state(s);
   HIPCHK(hipMemcpyAsync(&b->d_state[stream], &s, sizeof(s), hipMemcpyHostToDevice, b->stream));
-  /* lpcnet_plc_reset clears plc_net with the synthesis state */
-  if (b->plc_ok) {
-    const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-    HIPCHK(hipMemsetAsync(b->d_plc_state + (size_t)stream * nt, 0, nt * 4, b->stream));
-  }
-  /* and the analysis state (lpcnet_encoder_init inside lpcnet_plc_reset) */
-  if (b->d_feat_state) HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
-  if (b->d_enc_vq) HIPCHK(hipMemsetAsync(b->d_enc_vq + (size_t)stream * NBANDS, 0, NBANDS * 4, b->stream));
+  /* lpcnet_plc_reset clears plc_net with the synthesis state, and the
+   * analysis state (lpcnet_encoder_init inside lpcnet_plc_reset) */
+  if (side_reset(b, stream, SIDE_PLC | SIDE_FEAT)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   b->min_fc = std::min(b->min_fc, s.frame_count);
   return 0;
@@ -799,9 +794,7 @@ LPCNET_EXPORT void lpcnet_batch_reset(LPCNetBatch *b)
   host_reset_state(v[0]);
   for (int i = 1; i < b->B; i++) v[i] = v[0];
   (void)hipMemcpyAsync(b->d_state, v.data(), sizeof(StreamState) * v.size(), hipMemcpyHostToDevice, b->stream);
-  if (b->plc_ok) (void)hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * (b->pa.n1 + b->pa.n2) * 4, b->stream);
-  if (b->d_feat_state) (void)hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream);
-  if (b->d_enc_vq) (void)hipMemsetAsync(b->d_enc_vq, 0, (size_t)b->B * NBANDS * 4, b->stream);
+  (void)side_reset(b, -1, SIDE_PLC | SIDE_FEAT);
   (void)hipStreamSynchronize(b->stream);
   b->min_fc = v[0].frame_count;
 }

@@ -41,7 +41,6 @@ constexpr int WIN = LPC_WIN;
 constexpr int HALF = FRAME / 2;      /* TRAINING_OFFSET, and the half-frame of the pitch search */
 constexpr int EXC = PITCH_MAX + FRAME; /* exc_buf entries the single-frame path touches */
 constexpr int NST = PITCH_STATES;
-constexpr float PREEMPH_COEF = 0.85f; /* freq.h:34 PREEMPHASIS */
 /* per-stream scratch floats */
 constexpr int SM_EX = 0;    /* [NBANDS] band energies, then their logs */
 constexpr int SM_CEPS = 18; /* [NBANDS] */
@@ -52,16 +51,6 @@ constexpr int SM_N = 64;
 constexpr int YF_ENER = 0;   /* [2][PITCH_MAX] `ener` of every lag; later [PITCH_MAX] pitch_max_path[0] */
 constexpr int YF_PREV = 512; /* [2][NST] bytes: pitch_prev */
 static_assert(YF_PREV * 4 + 2 * NST <= WIN * 8, "pitch_prev fits the FFT buffer");
-
-#define FMAX16(a, b) ((a) > (b) ? (a) : (b)) /* arch.h:73 */
-
-/* kiss_fft's input permutation for factors (4,4,4,5): sample n = d0 + 5 d1 +
- * 20 d2 + 80 d3 feeds FFT slot 64 d0 + 16 d1 + 4 d2 + d3 (build_lpc_tables) */
-__device__ __forceinline__ int fft_slot(int n)
-{
-  const int d3 = n / 80, r = n % 80, d2 = r / 20, r2 = r % 20, d1 = r2 / 5, d0 = r2 % 5;
-  return 64 * d0 + 16 * d1 + 4 * d2 + d3;
-}
 
 }  // namespace
 
@@ -92,16 +81,8 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
   const bool live = sid < A.nstreams && (!A.active || A.active[sid]); /* wave-uniform */
   if (lane == 0) liveb[w] = live;
   const LpcTables *T = A.lpc_tab;
-  for (int k = threadIdx.x; k < WIN; k += blockDim.x) {
-    tw[k] = C2{T->twr[k], T->twi[k]};
-    slot[k] = T->slot[k];
-  }
-  for (int k = threadIdx.x; k < NBANDS * NBANDS; k += blockDim.x) dct[k] = T->dct[k];
-  for (int k = threadIdx.x; k < FRAME; k += blockDim.x) {
-    hwin[k] = A.tab->half_window[k];
-    frac[k] = A.tab->frac[k];
-  }
-  if (threadIdx.x < NBANDS) bstart[threadIdx.x] = A.tab->band_start[threadIdx.x];
+  stage_fft_dct<true>(T, tw, dct, slot);
+  stage_bands<true>(A.tab, frac, bstart, hwin);
   const double sq = T->sqrt_2_18;
   const float cmp = lane < NBANDS ? T->comp[lane] : 0.f, scale = T->scale;
   FeatState *S = A.state + (live ? sid : 0);
@@ -147,23 +128,9 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
   __syncthreads();
   fft320_stages(live, lane, y, tw);
 
-  /* lpcn_compute_band_energy (freq.c:131-154): sum[b] takes segment b-1's
-   * frac terms, then segment b's (1-frac) terms, each in j order */
+  /* lpcn_compute_band_energy (freq.c:131-154), lpc_stages.h's walk */
   if (live && lane < NBANDS) {
-    float sum = 0;
-    if (lane > 0)
-      for (int k = bstart[lane - 1]; k < bstart[lane]; k++) {
-        float tmp = y[k].r * y[k].r;
-        tmp += y[k].i * y[k].i;
-        sum += frac[k] * tmp;
-      }
-    if (lane < NBANDS - 1)
-      for (int k = bstart[lane]; k < bstart[lane + 1]; k++) {
-        float tmp = y[k].r * y[k].r;
-        tmp += y[k].i * y[k].i;
-        sum += (1 - frac[k]) * tmp;
-      }
-    if (lane == 0 || lane == NBANDS - 1) sum *= 2;
+    const float sum = band_energy_walk(lane, y, frac, bstart, [](float p) { return p; });
     /* log10(1e-2+Ex[i]) in double, rounded to float (lpcnet_enc.c:515) */
     sm[SM_EX + lane] = (float)log10(1e-2 + (double)sum);
   }
@@ -176,9 +143,9 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
 #pragma unroll
     for (int i = 0; i < NBANDS; i++) {
       float ly = sm[SM_EX + i];
-      ly = FMAX16(logMax - 8, FMAX16(follow - 2.5f, ly));
-      logMax = FMAX16(logMax, ly);
-      follow = FMAX16(follow - 2.5f, ly);
+      ly = MAX16(logMax - 8, MAX16(follow - 2.5f, ly));
+      logMax = MAX16(logMax, ly);
+      follow = MAX16(follow - 2.5f, ly);
       acc += ly * dct[i * NBANDS + lane];
     }
     float c = (float)((double)acc * sq);
@@ -299,7 +266,7 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
             val1 += xc[sub][i - 3 + j] * interp[j];
             val2 += xc[sub][i + 3 - j] * interp[j];
           }
-          nv[sub][t] = FMAX16(xc[sub][i], FMAX16(val1, val2));
+          nv[sub][t] = MAX16(xc[sub][i], MAX16(val1, val2));
         }
       }
     if constexpr (SUPER) {
@@ -334,20 +301,10 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
 #pragma unroll
       for (int t = 0; t < 4; t++) xc[sub][lane + 64 * t] = nv[sub][t];
   __syncthreads();
-  /* the sub-harmonic check (lpcnet_enc.c:827-830) reads entries above i only
-   * ((PITCH_MAX+i-1)/2 > i for i < 192), which the serial loop has not scaled
-   * yet: every read before any write */
+  /* the sub-harmonic check (lpcnet_enc.c:827-830): every read before any write */
   if (live)
 #pragma unroll
-    for (int sub = 0; sub < 2; sub++)
-#pragma unroll
-      for (int t = 0; t < 3; t++) {
-        const int i = lane + 64 * t;
-        const float *r = xc[sub];
-        const float xc_half = FMAX16(FMAX16(r[(PITCH_MAX + i) / 2], r[(PITCH_MAX + i + 2) / 2]), r[(PITCH_MAX + i - 1) / 2]);
-        nv[sub][t] = r[i];
-        if (r[i] < xc_half * 1.1f) nv[sub][t] = r[i] * .8f;
-      }
+    for (int sub = 0; sub < 2; sub++) subharmonic_row(xc[sub], lane, nv[sub]);
   __syncthreads();
   if (live)
 #pragma unroll
@@ -370,57 +327,7 @@ __global__ __launch_bounds__(64 * FS) void feat_kernel(FeatArgs A)
   float max_all = live ? S->pitch_max_path_all : 0.f;
   int best_i = live ? S->best_i : 0;
 #pragma unroll
-  for (int sub = 0; sub < 2; sub++) {
-    float pv[4] = {0.f, 0.f, 0.f, 0.f};
-    float cur = -1e15f;
-    int cur_i = 0;
-    if (live) {
-#pragma unroll
-      for (int t = 0; t < 4; t++) {
-        const int i = lane + 64 * t;
-        if (i < NST) {
-          float max_prev = max_all - 6.f;
-          int pp = best_i;
-#pragma unroll
-          for (int j = -4; j <= 4; j++)
-            if (j >= -i && i + j < NST) {
-              const int aj = j < 0 ? -j : j;
-              const float v = pmp[i + j] - .02f * aj * aj;
-              if (v > max_prev) {
-                max_prev = v;
-                pp = i + j;
-              }
-            }
-          pprev[sub * NST + i] = (unsigned char)pp;
-          pv[t] = max_prev + fw[sub] * xc[sub][i];
-          if (pv[t] > cur) {
-            cur = pv[t];
-            cur_i = i;
-          }
-        }
-      }
-      /* the first index of the maximum, as the serial strict > keeps it */
-#pragma unroll
-      for (int m = 1; m < 64; m <<= 1) {
-        const float ov = __shfl_xor(cur, m, 64);
-        const int oi = __shfl_xor(cur_i, m, 64);
-        if (ov > cur || (ov == cur && oi < cur_i)) {
-          cur = ov;
-          cur_i = oi;
-        }
-      }
-    }
-    __syncthreads();
-    if (live) {
-      /* renormalise; RNN_COPY's entries beyond NST are never written: they keep their zeros */
-#pragma unroll
-      for (int t = 0; t < 4; t++)
-        if (lane + 64 * t < NST) pmp[lane + 64 * t] = pv[t] - cur;
-      max_all = cur;
-      best_i = cur_i;
-    }
-    __syncthreads();
-  }
+  for (int sub = 0; sub < 2; sub++) viterbi_step(live, lane, pmp, xc[sub], fw[sub], pprev + sub * NST, max_all, best_i);
 
   if (live) {
     /* backward pass (lpcnet_enc.c:856-866) */

@@ -13,7 +13,8 @@
  *                                         stages, digit-reversed scaled input
  *   lpc_from_bands       freq.c:275-297   noise floor + lag window (double)
  *   lpcn_lpc             freq.c:86-127    Levinson-Durbin, float build, lane 0
- * The stages live in lpc_stages.h, which feat_kernel.hip shares.
+ * The stages live in lpc_stages.h, which feat_kernel.hip, burg_kernel.hip and
+ * enc_kernel.hip share.
  * Must be compiled with -ffp-contract=off.  The output feeds the frame
  * kernel's two-frame LPC ring (lpcnet.c:110-112), so this kernel is two
  * frames ahead of its first use.
@@ -71,11 +72,7 @@ __global__ __launch_bounds__(64 * LPC_STREAMS) void lpc_kernel(const float *feat
 #pragma unroll
     for (int j = 0; j < NBANDS; j++) ceps[j] = c[j];
   }
-  for (int k = threadIdx.x; k < WIN; k += blockDim.x) {
-    tw[k] = C2{T->twr[k], T->twi[k]};
-    slot[k] = T->slot[k];
-  }
-  for (int k = threadIdx.x; k < NBANDS * NBANDS; k += blockDim.x) dct[k] = T->dct[k];
+  stage_fft_dct<true>(T, tw, dct, slot);
   const double sq = T->sqrt_2_18;
   const float cmp = lane < NBANDS ? T->comp[lane] : 0.f, scale = T->scale;
   C2 *y = ybuf[w];

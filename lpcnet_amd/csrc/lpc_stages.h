@@ -1,9 +1,13 @@
 /*
- * lpc_stages.h -- the device stages lpc_kernel.hip and feat_kernel.hip share:
- * the Opus 320-point kiss FFT (factors 4,4,4,5; kiss_fft.c:101-305, 518-586)
- * and lpc_from_cepstrum (freq.c:310-320) as workgroup-wide stages, one
- * wavefront per stream.  Every stage ends in __syncthreads(): all threads of
- * the workgroup must call them, live stream or not.
+ * lpc_stages.h -- the device stages lpc_kernel.hip, feat_kernel.hip,
+ * burg_kernel.hip and enc_kernel.hip share, one wavefront per stream:
+ *   the constant tables' staging into LDS, the FFT's input permutation
+ *   the Opus 320-point kiss FFT (factors 4,4,4,5; kiss_fft.c:101-305, 518-586)
+ *   lpc_from_cepstrum (freq.c:310-320)
+ *   the band-energy walk of lpcn_compute_band_energy and its inverse form
+ *   the pitch search's sub-harmonic check and Viterbi forward step
+ * The stages that end in __syncthreads() say so: all threads of the
+ * workgroup must call them, live stream or not.
  * Must be compiled with -ffp-contract=off.
  */
 #ifndef LPCNET_LPC_STAGES_H
@@ -18,9 +22,52 @@ namespace lpcnet_mi355x {
 
 namespace {
 
+#define MAX16(a, b) ((a) > (b) ? (a) : (b)) /* arch.h:73 */
+#define MIN16(a, b) ((a) < (b) ? (a) : (b)) /* arch.h:72 */
+
+constexpr float PREEMPH_COEF = 0.85f; /* freq.h:34 PREEMPHASIS */
+
 struct alignas(8) C2 {
   float r, i;
 };
+
+/* The constant tables into a workgroup's LDS, every thread of it a share; the
+ * caller's next __syncthreads() makes them stand.  Which tables a kernel has
+ * is a template argument, not a null pointer: a run-time test of an LDS
+ * pointer stays in the loop and keeps it from unrolling (feat_kernel<true>
+ * +1.2 % at 32,768 streams, profiles/r18).
+ * The FFT's twiddles, with SLOTS the band and fraction of every FFT slot
+ * (interp_band_gain) in the same loop -- a loop each costs lpc_kernel 14 VGPRs
+ * and two waves per SIMD -- and the dct matrix: */
+template <bool SLOTS>
+__device__ __forceinline__ void stage_fft_dct(const LpcTables *T, C2 *tw, float *dct, LpcSlot *slot)
+{
+  for (int k = threadIdx.x; k < LPC_WIN; k += blockDim.x) {
+    tw[k] = C2{T->twr[k], T->twi[k]};
+    if constexpr (SLOTS) slot[k] = T->slot[k];
+  }
+  for (int k = threadIdx.x; k < NBANDS * NBANDS; k += blockDim.x) dct[k] = T->dct[k];
+}
+
+/* the band-energy walk's fractions and band starts, with WINDOW the analysis
+ * window's rising half */
+template <bool WINDOW>
+__device__ __forceinline__ void stage_bands(const FeatTables *F, float *frac, int *bstart, float *hwin)
+{
+  for (int k = threadIdx.x; k < FRAME; k += blockDim.x) {
+    if constexpr (WINDOW) hwin[k] = F->half_window[k];
+    frac[k] = F->frac[k];
+  }
+  if (threadIdx.x < NBANDS) bstart[threadIdx.x] = F->band_start[threadIdx.x];
+}
+
+/* kiss_fft's input permutation for factors (4,4,4,5): sample n = d0 + 5 d1 +
+ * 20 d2 + 80 d3 feeds FFT slot 64 d0 + 16 d1 + 4 d2 + d3 (build_lpc_tables) */
+__device__ __forceinline__ int fft_slot(int n)
+{
+  const int d3 = n / 80, r = n % 80, d2 = r / 20, r2 = r % 20, d1 = r2 / 5, d0 = r2 % 5;
+  return 64 * d0 + 16 * d1 + 4 * d2 + d3;
+}
 
 __device__ __forceinline__ C2 cmul(C2 a, C2 b) { return C2{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
 __device__ __forceinline__ C2 cadd(C2 a, C2 b) { return C2{a.r + b.r, a.i + b.i}; }
@@ -183,6 +230,107 @@ __device__ __forceinline__ void levinson16(const float *acs, float (&lpc)[LPC_OR
       if (err < .001f * ac[0]) break;
     }
   }
+}
+
+/* The walk of lpcn_compute_band_energy (freq.c:131-154) and
+ * compute_band_energy_inverse (freq.c:60-84) for one band on one lane: sum
+ * takes segment band-1's frac terms, then segment band's (1-frac) terms, each
+ * in bin order; the end bands count twice.  term(|y|^2 as the reference sums
+ * it) is what a bin contributes. */
+template <class Term>
+__device__ __forceinline__ float band_energy_walk(int band, const C2 *y, const float *frac, const int *bstart, Term term)
+{
+  float sum = 0;
+  if (band > 0)
+    for (int k = bstart[band - 1]; k < bstart[band]; k++) {
+      float tmp = y[k].r * y[k].r;
+      tmp += y[k].i * y[k].i;
+      sum += frac[k] * term(tmp);
+    }
+  if (band < NBANDS - 1)
+    for (int k = bstart[band]; k < bstart[band + 1]; k++) {
+      float tmp = y[k].r * y[k].r;
+      tmp += y[k].i * y[k].i;
+      sum += (1 - frac[k]) * term(tmp);
+    }
+  if (band == 0 || band == NBANDS - 1) sum *= 2;
+  return sum;
+}
+
+/* The sub-harmonic check of one xc row r (lpcnet_enc.c:607-610, 827-830), a
+ * lane's entries lane + 64 t, t < 3, into nv.  It reads entries above i only
+ * ((PITCH_MAX+i-1)/2 > i for i < 192), which the reference's serial loop has
+ * not scaled yet: every read before any write, so the caller stores nv to the
+ * row behind a __syncthreads(). */
+__device__ __forceinline__ void subharmonic_row(const float *r, int lane, float *nv)
+{
+#pragma unroll
+  for (int t = 0; t < 3; t++) {
+    const int i = lane + 64 * t;
+    const float xc_half = MAX16(MAX16(r[(PITCH_MAX + i) / 2], r[(PITCH_MAX + i + 2) / 2]), r[(PITCH_MAX + i - 1) / 2]);
+    nv[t] = r[i];
+    if (r[i] < xc_half * 1.1f) nv[t] = r[i] * .8f;
+  }
+}
+
+/* One forward step of the pitch Viterbi search over one xc row with frame
+ * weight fw (lpcnet_enc.c:604-635, 831-855), lane per state, strict >
+ * everywhere: pmp [PITCH_STATES] is the wave's pitch_max_path, pprev
+ * [PITCH_STATES] takes this row's pitch_prev, max_all / best_i carry
+ * pitch_max_path_all and its index from row to row.  Two __syncthreads(). */
+__device__ __forceinline__ void viterbi_step(bool live, int lane, float *pmp, const float *xc, float fw, unsigned char *pprev,
+                                             float &max_all, int &best_i)
+{
+  constexpr int NST = PITCH_STATES;
+  float pv[4] = {0.f, 0.f, 0.f, 0.f};
+  float cur = -1e15f;
+  int cur_i = 0;
+  if (live) {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int i = lane + 64 * t;
+      if (i < NST) {
+        float max_prev = max_all - 6.f;
+        int pp = best_i;
+#pragma unroll
+        for (int j = -4; j <= 4; j++)
+          if (j >= -i && i + j < NST) {
+            const int aj = j < 0 ? -j : j;
+            const float v = pmp[i + j] - .02f * aj * aj;
+            if (v > max_prev) {
+              max_prev = v;
+              pp = i + j;
+            }
+          }
+        pprev[i] = (unsigned char)pp;
+        pv[t] = max_prev + fw * xc[i];
+        if (pv[t] > cur) {
+          cur = pv[t];
+          cur_i = i;
+        }
+      }
+    }
+    /* the first index of the maximum, as the serial strict > keeps it */
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      const float ov = __shfl_xor(cur, m, 64);
+      const int oi = __shfl_xor(cur_i, m, 64);
+      if (ov > cur || (ov == cur && oi < cur_i)) {
+        cur = ov;
+        cur_i = oi;
+      }
+    }
+  }
+  __syncthreads();
+  if (live) {
+    /* renormalise; RNN_COPY's entries beyond NST are never written: they keep their zeros */
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+      if (lane + 64 * t < NST) pmp[lane + 64 * t] = pv[t] - cur;
+    max_all = cur;
+    best_i = cur_i;
+  }
+  __syncthreads();
 }
 
 }  // namespace

@@ -18,18 +18,50 @@
 
 namespace {
 
-/* rows [B][row] of staging d_rows back to the caller's buffer, after every
- * command queued on b->stream: inactive streams keep their row */
-int copy_back_active(LPCNetBatch *b, const float *d_rows, int row, float *out, const unsigned char *active)
+/* rows [B] of `row` bytes of staging d_rows back to the caller's buffer, after
+ * every command queued on b->stream: inactive streams keep their row */
+int copy_back_active(LPCNetBatch *b, const void *d_rows, size_t row, void *out, const unsigned char *active)
 {
   const size_t B = (size_t)b->B;
-  std::vector<float> tmp(B * row);
-  HIPCHK(hipMemcpyAsync(tmp.data(), d_rows, tmp.size() * 4, hipMemcpyDeviceToHost, b->stream));
+  std::vector<char> tmp(B * row);
+  HIPCHK(hipMemcpyAsync(tmp.data(), d_rows, tmp.size(), hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   for (size_t s = 0; s < B; s++)
-    if (!active || active[s]) memcpy(out + s * row, &tmp[s * row], (size_t)row * 4);
+    if (!active || active[s]) memcpy((char *)out + s * row, &tmp[s * row], row);
   return 0;
 }
+
+/* One device allocation carved into 256-byte-aligned parts: add(p, n) plans n
+ * elements behind the pointer p; alloc() allocates the whole, sets every
+ * planned pointer and returns the base (null, the pointers untouched, when the
+ * device refuses). */
+class Carver {
+  struct Part {
+    void *ptr; /* the T * to set */
+    size_t off;
+  };
+  std::vector<Part> parts;
+  size_t bytes = 0;
+
+ public:
+  template <class T>
+  void add(T *&p, size_t n)
+  {
+    parts.push_back({&p, bytes});
+    bytes += (n * sizeof(T) + 255) & ~(size_t)255;
+  }
+  size_t size() const { return bytes; }
+  void *alloc()
+  {
+    char *base = nullptr;
+    if (hipMalloc(&base, bytes) != hipSuccess) return nullptr;
+    for (const Part &q : parts) {
+      char *p = base + q.off;
+      memcpy(q.ptr, &p, sizeof(p));
+    }
+    return base;
+  }
+};
 
 }  // namespace
 
@@ -40,8 +72,7 @@ void plc_free(LPCNetBatch *b)
 {
   for (void *p : b->plc_bufs) (void)hipFree(p);
   b->plc_bufs.clear();
-  b->d_plc_state = b->d_plc_in = b->d_plc_out = nullptr;
-  b->d_plc_act = nullptr;
+  b->plc = {};
   b->plc_ok = false;
   b->pa = PlcArgs{};
 }
@@ -70,10 +101,10 @@ void plc_load(LPCNetBatch *b, const std::vector<Arr> &L)
     const void *p = up(u.src, u.bytes);
     memcpy(u.dst, &p, sizeof(p));
   }
-  a.state = b->d_plc_state = (float *)up(nullptr, (size_t)b->B * (a.n1 + a.n2) * 4);
-  b->d_plc_in = (float *)up(nullptr, (size_t)b->B * PLC_IN * 4);
-  b->d_plc_out = (float *)up(nullptr, (size_t)b->B * NF * 4);
-  b->d_plc_act = (unsigned char *)up(nullptr, (size_t)b->B);
+  a.state = b->plc.state = (float *)up(nullptr, (size_t)b->B * (a.n1 + a.n2) * 4);
+  b->plc.in = (float *)up(nullptr, (size_t)b->B * PLC_IN * 4);
+  b->plc.out = (float *)up(nullptr, (size_t)b->B * NF * 4);
+  b->plc.act = (unsigned char *)up(nullptr, (size_t)b->B);
   if (!ok) {
     plc_free(b);
     b->plc_why = "PLC: device allocation or upload of the predictor tables failed";
@@ -86,26 +117,26 @@ void plc_load(LPCNetBatch *b, const std::vector<Arr> &L)
 
 void feat_free(LPCNetBatch *b)
 {
-  (void)hipFree(b->d_feat_state);
-  (void)hipFree(b->d_feat_tab);
-  (void)hipFree(b->d_feat_pcm);
-  (void)hipFree(b->d_feat_out);
-  (void)hipFree(b->d_feat_act);
-  (void)hipFree(b->d_enc_base);
-  (void)hipFree(b->d_burg_tab);
-  b->d_burg_tab = nullptr;
-  b->d_burg_c = nullptr;
-  b->d_burg_x = b->d_burg_o = nullptr;
-  b->d_enc_base = nullptr;
-  b->d_enc_vq = b->d_enc_xc = b->d_enc_fw = b->d_enc_feat = b->d_enc_lpc = b->d_enc_out = nullptr;
-  b->d_enc_tab = nullptr;
-  b->d_enc_fields = nullptr;
-  b->d_enc_pcm = nullptr;
-  b->d_enc_pk = nullptr;
-  b->d_feat_state = nullptr;
-  b->d_feat_tab = nullptr;
-  b->d_feat_pcm = b->d_feat_out = nullptr;
-  b->d_feat_act = nullptr;
+  (void)hipFree(b->feat.base);
+  (void)hipFree(b->burg.base);
+  (void)hipFree(b->enc.base);
+  b->feat = {};
+  b->burg = {};
+  b->enc = {};
+}
+
+int side_reset(LPCNetBatch *b, int stream, int parts)
+{
+  const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)b->B : 1;
+  if ((parts & SIDE_PLC) && b->plc_ok) {
+    const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
+    HIPCHK(hipMemsetAsync(b->plc.state + first * nt, 0, n * nt * 4, b->stream));
+  }
+  if ((parts & SIDE_FEAT) && b->feat.state) {
+    HIPCHK(hipMemsetAsync(b->feat.state + first, 0, n * sizeof(FeatState), b->stream));
+    if (b->enc.vq) HIPCHK(hipMemsetAsync(b->enc.vq + first * NBANDS, 0, n * NBANDS * 4, b->stream));
+  }
+  return 0;
 }
 
 }  // namespace lpcnet_mi355x
@@ -153,23 +184,21 @@ LPCNET_EXPORT int lpcnet_batch_plc_predict(LPCNetBatch *b, const float *in, floa
 {
   if (plc_ready(b) || b->set_device()) return -1;
   const size_t B = (size_t)b->B;
-  if (in) HIPCHK(hipMemcpyAsync(b->d_plc_in, in, B * PLC_IN * 4, hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_plc_act, active, B, hipMemcpyHostToDevice, b->stream));
-  if (plc_launch(b, in ? b->d_plc_in : nullptr, out ? b->d_plc_out : nullptr, active ? b->d_plc_act : nullptr)) return -1;
+  if (in) HIPCHK(hipMemcpyAsync(b->plc.in, in, B * PLC_IN * 4, hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->plc.act, active, B, hipMemcpyHostToDevice, b->stream));
+  if (plc_launch(b, in ? b->plc.in : nullptr, out ? b->plc.out : nullptr, active ? b->plc.act : nullptr)) return -1;
   if (!out) {
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
   }
-  return copy_back_active(b, b->d_plc_out, NF, out, active);
+  return copy_back_active(b, b->plc.out, NF * 4, out, active);
 }
 
 LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int stream)
 {
   if (plc_ready(b) || b->set_device()) return -1;
   if (stream < -1 || stream >= b->B) { set_err("no such stream"); return -1; }
-  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-  if (stream < 0) HIPCHK(hipMemsetAsync(b->d_plc_state, 0, (size_t)b->B * nt * 4, b->stream));
-  else HIPCHK(hipMemsetAsync(b->d_plc_state + (size_t)stream * nt, 0, nt * 4, b->stream));
+  if (side_reset(b, stream, SIDE_PLC)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -186,7 +215,7 @@ LPCNET_EXPORT int lpcnet_batch_plc_save_state(LPCNetBatch *b, int stream, void *
   if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
   const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
   HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, b->d_plc_state + (size_t)stream * nt, nt * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(buf, b->plc.state + (size_t)stream * nt, nt * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -202,7 +231,7 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
     return -1;
   }
   HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(b->d_plc_state + (size_t)stream * nt, buf, nt * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->plc.state + (size_t)stream * nt, buf, nt * 4, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -213,39 +242,44 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
 /* the analysis state, tables and staging of a batch, on its first extraction */
 static int feat_ensure(LPCNetBatch *b)
 {
-  if (b->d_feat_state) return 0;
+  if (b->feat.base) return 0;
   const size_t B = (size_t)b->B;
+  FeatBufs f{};
+  Carver c;
+  c.add(f.state, B);
+  c.add(f.tab, 1);
+  c.add(f.pcm, B * FRAME);
+  c.add(f.out, B * NTF);
+  c.add(f.act, B);
   FeatTables T;
   build_feat_tables(T);
-  FeatState *st = nullptr;
-  FeatTables *tab = nullptr;
-  float *pcm = nullptr, *out = nullptr;
-  unsigned char *act = nullptr;
-  const bool ok = hipMalloc(&st, sizeof(FeatState) * B) == hipSuccess &&
-                  hipMemsetAsync(st, 0, sizeof(FeatState) * B, b->stream) == hipSuccess && /* ordered before the first launch */
-                  hipMalloc(&tab, sizeof(T)) == hipSuccess && hipMemcpy(tab, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMalloc(&pcm, B * FRAME * 4) == hipSuccess && hipMalloc(&out, B * NTF * 4) == hipSuccess &&
-                  hipMalloc(&act, B) == hipSuccess;
-  if (!ok) {
-    (void)hipFree(st);
-    (void)hipFree(tab);
-    (void)hipFree(pcm);
-    (void)hipFree(out);
-    (void)hipFree(act);
+  f.base = c.alloc();
+  if (!f.base || hipMemsetAsync(f.state, 0, sizeof(FeatState) * B, b->stream) != hipSuccess || /* ordered before the first launch */
+      hipMemcpy(f.tab, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(f.base);
     set_err("features: device allocation failed");
     return -1;
   }
-  b->d_feat_state = st;
-  b->d_feat_tab = tab;
-  b->d_feat_pcm = pcm;
-  b->d_feat_out = out;
-  b->d_feat_act = act;
+  b->feat = f;
   return 0;
 }
 
-/* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
-static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
-                       const unsigned char *d_active, int stride = 0)
+/* the caller's PCM (or what it was rearranged to) into d_dst and its active
+ * mask into the extractor's staging, queued on b->stream; d_active: the mask
+ * the launches take */
+static int stage_in(LPCNetBatch *b, void *d_dst, const void *src, size_t bytes, const unsigned char *active,
+                    const unsigned char *&d_active)
+{
+  HIPCHK(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->feat.act, active, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
+  d_active = active ? b->feat.act : nullptr;
+  return 0;
+}
+
+/* the extractor's arguments on a batch: one frame of d_pcm (short) or d_pcm_f
+ * into rows of `row` values, `stride` apart */
+static FeatArgs feat_args(const LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row, int stride,
+                          const unsigned char *d_active)
 {
   FeatArgs a{};
   a.nstreams = b->B;
@@ -253,11 +287,20 @@ static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f,
   a.pcm_f = d_pcm_f;
   a.features = d_features;
   a.row = row;
-  a.stride = stride ? stride : row; /* the dense [B][row] of every call but the predictor rows */
+  a.stride = stride;
   a.active = d_active;
-  a.state = b->d_feat_state;
+  a.state = b->feat.state;
   a.lpc_tab = b->d_lpc_tab;
-  a.tab = b->d_feat_tab;
+  a.tab = b->feat.tab;
+  return a;
+}
+
+/* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
+static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
+                       const unsigned char *d_active, int stride = 0)
+{
+  /* stride 0: the dense [B][row] of every call but the predictor rows */
+  const FeatArgs a = feat_args(b, d_pcm, d_pcm_f, d_features, row, stride ? stride : row, d_active);
   return timed_launch(b, 3, b->timing != 0, 1, "feature kernel launch failed", [&] { return launch_feat(a, b->stream); });
 }
 
@@ -266,13 +309,45 @@ static int feat_host(LPCNetBatch *b, const void *pcm, bool is_float, float *feat
   if (!pcm || !features) { set_err("bad arguments"); return -1; }
   if (!b) { set_err("null batch"); return -1; }
   if (b->set_device() || feat_ensure(b)) return -1;
-  const size_t B = (size_t)b->B;
-  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * (is_float ? 4 : 2), hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
-  if (feat_launch(b, is_float ? nullptr : (const short *)b->d_feat_pcm, is_float ? b->d_feat_pcm : nullptr, b->d_feat_out, NTF,
-                  active ? b->d_feat_act : nullptr))
-    return -1;
-  return copy_back_active(b, b->d_feat_out, NTF, features, active);
+  const unsigned char *d_act;
+  if (stage_in(b, b->feat.pcm, pcm, (size_t)b->B * FRAME * (is_float ? 4 : 2), active, d_act)) return -1;
+  if (feat_launch(b, is_float ? nullptr : (const short *)b->feat.pcm, is_float ? b->feat.pcm : nullptr, b->feat.out, NTF, d_act)) return -1;
+  return copy_back_active(b, b->feat.out, NTF * 4, features, active);
+}
+
+/* What the analysis-state snapshot calls (features, encoder) check, in the
+ * contract's order: the stream index and the buffer, a restored snapshot's
+ * best_i (the kernel indexes its Viterbi rows with it; restore_of names the
+ * snapshot in the error), the batch, the stream against it; then the device,
+ * the family's buffers and a quiet stream. */
+static int snap_ready(LPCNetBatch *b, int stream, const void *buf, const char *restore_of, int (*ensure)(LPCNetBatch *))
+{
+  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
+  if (restore_of) {
+    FeatState s;
+    memcpy(&s, buf, sizeof(s));
+    if (s.best_i < 0 || s.best_i >= PITCH_STATES) {
+      set_err(std::string(restore_of) + " snapshot: best_i outside [0, 224): not a state this engine produced");
+      return -1;
+    }
+  }
+  if (!b) { set_err("null batch"); return -1; }
+  if (stream >= b->B) { set_err("no such stream"); return -1; }
+  if (b->set_device() || ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+static int feat_state_save(LPCNetBatch *b, int stream, void *buf)
+{
+  HIPCHK(hipMemcpy(buf, b->feat.state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+static int feat_state_restore(LPCNetBatch *b, int stream, const void *buf)
+{
+  HIPCHK(hipMemcpy(b->feat.state + stream, buf, sizeof(FeatState), hipMemcpyHostToDevice));
+  return 0;
 }
 
 extern "C" {
@@ -307,14 +382,8 @@ LPCNET_EXPORT int lpcnet_batch_features_reset(LPCNetBatch *b, int stream)
   if (stream < -1) { set_err("no such stream"); return -1; }
   if (!b) { set_err("null batch"); return -1; }
   if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (!b->d_feat_state) return 0; /* never used: a first use starts from the reset state */
-  if (b->set_device()) return -1;
-  if (stream < 0) HIPCHK(hipMemsetAsync(b->d_feat_state, 0, sizeof(FeatState) * (size_t)b->B, b->stream));
-  else HIPCHK(hipMemsetAsync(b->d_feat_state + stream, 0, sizeof(FeatState), b->stream));
-  if (b->d_enc_vq) {
-    if (stream < 0) HIPCHK(hipMemsetAsync(b->d_enc_vq, 0, (size_t)b->B * NBANDS * 4, b->stream));
-    else HIPCHK(hipMemsetAsync(b->d_enc_vq + (size_t)stream * NBANDS, 0, NBANDS * 4, b->stream));
-  }
+  if (!b->feat.state) return 0; /* never used: a first use starts from the reset state */
+  if (b->set_device() || side_reset(b, stream, SIDE_FEAT)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -323,62 +392,44 @@ LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *) { return
 
 LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf)
 {
-  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (b->set_device() || feat_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, b->d_feat_state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
-  return 0;
+  if (snap_ready(b, stream, buf, nullptr, feat_ensure)) return -1;
+  return feat_state_save(b, stream, buf);
 }
 
 LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf)
 {
-  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
-  /* the kernel indexes its Viterbi rows with best_i */
-  FeatState s;
-  memcpy(&s, buf, sizeof(s));
-  if (s.best_i < 0 || s.best_i >= PITCH_STATES) { set_err("features snapshot: best_i outside [0, 224): not a state this engine produced"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (b->set_device() || feat_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(b->d_feat_state + stream, &s, sizeof(s), hipMemcpyHostToDevice));
-  return 0;
+  if (snap_ready(b, stream, buf, "features", feat_ensure)) return -1;
+  return feat_state_restore(b, stream, buf);
 }
 
 }  // extern "C"
 
 /* ---- Burg cepstral analysis, the predictor's input rows (burg_kernel.hip) --- */
 
-static_assert(BURG_N == NTF, "the Burg calls stage their output in d_feat_out");
+static_assert(BURG_N == NTF, "the Burg calls stage their output in the extractor's out");
 
 /* the extractor's tables and staging, and in one buffer the Burg table and
  * the scratch its three stages hand over through, on a batch's first Burg call */
 static int burg_ensure(LPCNetBatch *b)
 {
   if (feat_ensure(b)) return -1;
-  if (b->d_burg_tab) return 0;
+  if (b->burg.base) return 0;
   const size_t n2 = 2 * (size_t)b->B;
-  size_t off = 0;
-  auto part = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_tab = part(sizeof(BurgTables)), o_c = part(BURG_NC * n2 * 8), o_x = part(2 * NLPC * n2 * 4), o_o = part((NLPC + 1) * n2 * 4);
+  BurgBufs g{};
+  Carver c;
+  c.add(g.tab, 1);
+  c.add(g.c, BURG_NC * n2);
+  c.add(g.x, 2 * NLPC * n2);
+  c.add(g.o, (NLPC + 1) * n2);
   BurgTables T;
   build_burg_tables(T);
-  char *base = nullptr;
-  if (hipMalloc(&base, off) != hipSuccess || hipMemcpy(base + o_tab, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(base);
+  g.base = c.alloc();
+  if (!g.base || hipMemcpy(g.tab, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(g.base);
     set_err("burg: device allocation failed");
     return -1;
   }
-  b->d_burg_tab = (BurgTables *)(base + o_tab); /* the buffer's start: feat_free frees it */
-  b->d_burg_c = (double *)(base + o_c);
-  b->d_burg_x = (float *)(base + o_x);
-  b->d_burg_o = (float *)(base + o_o);
+  b->burg = g;
   return 0;
 }
 
@@ -396,11 +447,11 @@ static int burg_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f,
   a.flag = flag;
   a.active = d_active;
   a.lpc_tab = b->d_lpc_tab;
-  a.tab = b->d_feat_tab;
-  a.btab = b->d_burg_tab;
-  a.cbuf = b->d_burg_c;
-  a.xbuf = b->d_burg_x;
-  a.obuf = b->d_burg_o;
+  a.tab = b->feat.tab;
+  a.btab = b->burg.tab;
+  a.cbuf = b->burg.c;
+  a.xbuf = b->burg.x;
+  a.obuf = b->burg.o;
   return timed_launch(b, 6, b->timing != 0, 1, "Burg kernel launch failed", [&] { return launch_burg(a, b->stream); });
 }
 
@@ -409,13 +460,11 @@ static int burg_host(LPCNetBatch *b, const void *pcm, bool is_float, float *ceps
   if (!pcm || !ceps) { set_err("bad arguments"); return -1; }
   if (!b) { set_err("null batch"); return -1; }
   if (b->set_device() || burg_ensure(b)) return -1;
-  const size_t B = (size_t)b->B;
-  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * (is_float ? 4 : 2), hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
-  if (burg_launch(b, is_float ? nullptr : (const short *)b->d_feat_pcm, is_float ? b->d_feat_pcm : nullptr, b->d_feat_out, BURG_N, 0, 0.f,
-                  active ? b->d_feat_act : nullptr))
+  const unsigned char *d_act;
+  if (stage_in(b, b->feat.pcm, pcm, (size_t)b->B * FRAME * (is_float ? 4 : 2), active, d_act)) return -1;
+  if (burg_launch(b, is_float ? nullptr : (const short *)b->feat.pcm, is_float ? b->feat.pcm : nullptr, b->feat.out, BURG_N, 0, 0.f, d_act))
     return -1;
-  return copy_back_active(b, b->d_feat_out, BURG_N, ceps, active);
+  return copy_back_active(b, b->feat.out, BURG_N * 4, ceps, active);
 }
 
 /* one predictor input row per live stream on the batch's stream, no host
@@ -480,8 +529,8 @@ LPCNET_EXPORT int lpcnet_batch_plc_update_device(LPCNetBatch *b, const short *d_
   if (plc_ready(b)) return -1;
   if (!d_pcm || !d_out) { set_err("bad arguments"); return -1; }
   if (b->set_device() || burg_ensure(b)) return -1;
-  if (plc_rows(b, d_pcm, b->d_plc_in, LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES, 1.f, d_active)) return -1;
-  return plc_launch(b, b->d_plc_in, d_out, d_active);
+  if (plc_rows(b, d_pcm, b->plc.in, LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES, 1.f, d_active)) return -1;
+  return plc_launch(b, b->plc.in, d_out, d_active);
 }
 
 LPCNET_EXPORT int lpcnet_batch_plc_update(LPCNetBatch *b, const short *pcm, float *out, const unsigned char *active)
@@ -489,13 +538,11 @@ LPCNET_EXPORT int lpcnet_batch_plc_update(LPCNetBatch *b, const short *pcm, floa
   if (plc_ready(b)) return -1;
   if (!pcm || !out) { set_err("bad arguments"); return -1; }
   if (b->set_device() || burg_ensure(b)) return -1;
-  const size_t B = (size_t)b->B;
-  HIPCHK(hipMemcpyAsync(b->d_feat_pcm, pcm, B * FRAME * 2, hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
-  const unsigned char *d_act = active ? b->d_feat_act : nullptr;
-  if (plc_rows(b, (const short *)b->d_feat_pcm, b->d_plc_in, LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES, 1.f, d_act)) return -1;
-  if (plc_launch(b, b->d_plc_in, b->d_plc_out, d_act)) return -1;
-  return copy_back_active(b, b->d_plc_out, NF, out, active);
+  const unsigned char *d_act;
+  if (stage_in(b, b->feat.pcm, pcm, (size_t)b->B * FRAME * 2, active, d_act)) return -1;
+  if (plc_rows(b, (const short *)b->feat.pcm, b->plc.in, LPCNET_PLC_ROW_BURG | LPCNET_PLC_ROW_FEATURES, 1.f, d_act)) return -1;
+  if (plc_launch(b, b->plc.in, b->plc.out, d_act)) return -1;
+  return copy_back_active(b, b->plc.out, NF * 4, out, active);
 }
 
 }  // extern "C"
@@ -507,38 +554,31 @@ LPCNET_EXPORT int lpcnet_batch_plc_update(LPCNetBatch *b, const short *pcm, floa
 static int enc_ensure(LPCNetBatch *b)
 {
   if (feat_ensure(b)) return -1;
-  if (b->d_enc_base) return 0;
+  if (b->enc.base) return 0;
   const size_t B = (size_t)b->B;
-  size_t off = 0;
-  auto part = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_vq = part(B * NBANDS * 4), o_tab = part(sizeof(EncTables)), o_xc = part(B * 8 * PITCH_MAX * 4), o_fw = part(B * 8 * 4),
-               o_feat = part(4 * B * NF * 4), o_lpc = part(4 * B * NLPC * 4), o_fl = part(B * 4 * 4), o_pcm = part(4 * B * FRAME * 2),
-               o_pk = part(B * 8), o_out = part(4 * B * NTF * 4);
+  EncBufs n{};
+  Carver c;
+  c.add(n.vq, B * NBANDS);
+  c.add(n.tab, 1);
+  c.add(n.xc, B * 8 * PITCH_MAX);
+  c.add(n.fw, B * 8);
+  c.add(n.feat, 4 * B * NF);
+  c.add(n.lpc, 4 * B * NLPC);
+  c.add(n.fields, B * 4);
+  c.add(n.pcm, 4 * B * FRAME);
+  c.add(n.pk, B * 8);
+  c.add(n.out, 4 * B * NTF);
   EncTables T;
   build_enc_tables(T);
-  char *base = nullptr;
-  if (hipMalloc(&base, off) != hipSuccess || hipMemsetAsync(base, 0, off, b->stream) != hipSuccess ||
-      hipMemcpyAsync(base + o_tab, &T, sizeof(T), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
+  n.base = c.alloc();
+  if (!n.base || hipMemsetAsync(n.base, 0, c.size(), b->stream) != hipSuccess ||
+      hipMemcpyAsync(n.tab, &T, sizeof(T), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
       hipStreamSynchronize(b->stream) != hipSuccess) { /* T leaves scope */
-    (void)hipFree(base);
+    (void)hipFree(n.base);
     set_err("encode: device allocation failed");
     return -1;
   }
-  b->d_enc_base = base;
-  b->d_enc_vq = (float *)(base + o_vq);
-  b->d_enc_tab = (EncTables *)(base + o_tab);
-  b->d_enc_xc = (float *)(base + o_xc);
-  b->d_enc_fw = (float *)(base + o_fw);
-  b->d_enc_feat = (float *)(base + o_feat);
-  b->d_enc_lpc = (float *)(base + o_lpc);
-  b->d_enc_fields = (int *)(base + o_fl);
-  b->d_enc_pcm = (short *)(base + o_pcm);
-  b->d_enc_pk = (unsigned char *)(base + o_pk);
-  b->d_enc_out = (float *)(base + o_out);
+  b->enc = n;
   return 0;
 }
 
@@ -550,20 +590,11 @@ static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned
 {
   const size_t B = (size_t)b->B;
   for (int k = 0; k < 4; k++) {
-    FeatArgs a{};
-    a.nstreams = b->B;
-    a.pcm = d_pcm + k * B * FRAME;
-    a.features = b->d_enc_feat + k * B * NF;
-    a.row = NF;
-    a.stride = NF;
-    a.active = d_active;
-    a.state = b->d_feat_state;
-    a.lpc_tab = b->d_lpc_tab;
-    a.tab = b->d_feat_tab;
+    FeatArgs a = feat_args(b, d_pcm + k * B * FRAME, nullptr, b->enc.feat + k * B * NF, NF, NF, d_active);
     a.k = k;
-    a.xc_out = b->d_enc_xc;
-    a.fw_out = b->d_enc_fw;
-    a.lpc_out = b->d_enc_lpc + k * B * NLPC;
+    a.xc_out = b->enc.xc;
+    a.fw_out = b->enc.fw;
+    a.lpc_out = b->enc.lpc + k * B * NLPC;
     if (timed_launch(b, 4, b->timing != 0, 1, "encoder analysis kernel launch failed", [&] { return launch_feat_super(a, b->stream); }))
       return -1;
   }
@@ -571,14 +602,14 @@ static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned
   e.nstreams = b->B;
   e.quantize = quantize;
   e.active = d_active;
-  e.state = b->d_feat_state;
-  e.vq_mem = b->d_enc_vq;
-  e.xc = b->d_enc_xc;
-  e.fw = b->d_enc_fw;
-  e.feat = b->d_enc_feat;
-  e.fields = b->d_enc_fields;
-  e.lpc = b->d_enc_lpc;
-  e.tab = b->d_enc_tab;
+  e.state = b->feat.state;
+  e.vq_mem = b->enc.vq;
+  e.xc = b->enc.xc;
+  e.fw = b->enc.fw;
+  e.feat = b->enc.feat;
+  e.fields = b->enc.fields;
+  e.lpc = b->enc.lpc;
+  e.tab = b->enc.tab;
   if (quantize) {
     e.cb1 = b->da.cb1;
     e.cb2 = b->da.cb2;
@@ -596,7 +627,7 @@ static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned
     if (launch_enc_vq(e, b->stream)) { set_err("encoder quantiser kernel launch failed"); return -1; }
     /* lpc_from_cepstrum of the four quantised cepstra (lpcnet_enc.c:714-717);
      * unquantised, the analysis has left the same LPC */
-    if (d_features && row == NTF && launch_lpc(b->d_enc_feat, b->d_enc_lpc, 4 * b->B, b->d_lpc_tab, b->stream)) {
+    if (d_features && row == NTF && launch_lpc(b->enc.feat, b->enc.lpc, 4 * b->B, b->d_lpc_tab, b->stream)) {
       set_err("encoder LPC kernel launch failed");
       return -1;
     }
@@ -630,21 +661,13 @@ static int enc_host(LPCNetBatch *b, const short *pcm, int quantize, unsigned cha
   std::vector<short> t(4 * B * FRAME);
   for (size_t s = 0; s < B; s++)
     for (int k = 0; k < 4; k++) memcpy(&t[(k * B + s) * FRAME], pcm + s * 4 * FRAME + (size_t)k * FRAME, FRAME * 2);
-  HIPCHK(hipMemcpyAsync(b->d_enc_pcm, t.data(), t.size() * 2, hipMemcpyHostToDevice, b->stream));
-  if (active) HIPCHK(hipMemcpyAsync(b->d_feat_act, active, B, hipMemcpyHostToDevice, b->stream));
-  if (enc_packet(b, b->d_enc_pcm, quantize, quantize ? b->d_enc_pk : nullptr, features ? b->d_enc_out : nullptr, NTF,
-                 active ? b->d_feat_act : nullptr))
-    return -1;
-  if (quantize) {
-    std::vector<unsigned char> pk(B * 8);
-    HIPCHK(hipMemcpyAsync(pk.data(), b->d_enc_pk, pk.size(), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (size_t s = 0; s < B; s++)
-      if (!active || active[s]) memcpy(packets + s * 8, &pk[s * 8], 8);
-  }
+  const unsigned char *d_act;
+  if (stage_in(b, b->enc.pcm, t.data(), t.size() * 2, active, d_act)) return -1;
+  if (enc_packet(b, b->enc.pcm, quantize, quantize ? b->enc.pk : nullptr, features ? b->enc.out : nullptr, NTF, d_act)) return -1;
+  if (quantize && copy_back_active(b, b->enc.pk, 8, packets, active)) return -1;
   if (features)
     for (int k = 0; k < 4; k++)
-      if (copy_back_active(b, b->d_enc_out + k * B * NTF, NTF, features + k * B * NTF, active)) return -1;
+      if (copy_back_active(b, b->enc.out + k * B * NTF, NTF * 4, features + k * B * NTF, active)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream)); /* t and the staging are free again */
   return 0;
 }
@@ -682,30 +705,18 @@ LPCNET_EXPORT int lpcnet_batch_encode_device(LPCNetBatch *b, const short *d_pcm,
 
 LPCNET_EXPORT int lpcnet_batch_encode_state_size(const LPCNetBatch *) { return (int)sizeof(FeatState) + NBANDS * 4; }
 
+/* the features snapshot, then vq_mem */
 LPCNET_EXPORT int lpcnet_batch_encode_save_state(LPCNetBatch *b, int stream, void *buf)
 {
-  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (b->set_device() || enc_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, b->d_feat_state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy((char *)buf + sizeof(FeatState), b->d_enc_vq + (size_t)stream * NBANDS, NBANDS * 4, hipMemcpyDeviceToHost));
+  if (snap_ready(b, stream, buf, nullptr, enc_ensure) || feat_state_save(b, stream, buf)) return -1;
+  HIPCHK(hipMemcpy((char *)buf + sizeof(FeatState), b->enc.vq + (size_t)stream * NBANDS, NBANDS * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
 LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, const void *buf)
 {
-  if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
-  FeatState s;
-  memcpy(&s, buf, sizeof(s));
-  if (s.best_i < 0 || s.best_i >= PITCH_STATES) { set_err("encoder snapshot: best_i outside [0, 224): not a state this engine produced"); return -1; }
-  if (!b) { set_err("null batch"); return -1; }
-  if (stream >= b->B) { set_err("no such stream"); return -1; }
-  if (b->set_device() || enc_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(b->d_feat_state + stream, &s, sizeof(s), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->d_enc_vq + (size_t)stream * NBANDS, (const char *)buf + sizeof(FeatState), NBANDS * 4, hipMemcpyHostToDevice));
+  if (snap_ready(b, stream, buf, "encoder", enc_ensure) || feat_state_restore(b, stream, buf)) return -1;
+  HIPCHK(hipMemcpy(b->enc.vq + (size_t)stream * NBANDS, (const char *)buf + sizeof(FeatState), NBANDS * 4, hipMemcpyHostToDevice));
   return 0;
 }
 

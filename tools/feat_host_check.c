@@ -1,8 +1,12 @@
 /*
- * feat_host_check.c -- the host side of the feature-extraction calls that runs
- * without a device: argument checks, the snapshot size and the snapshot
- * validation of include/lpcnet_mi355x.h's lpcnet_batch_*features* calls.
- * A stand-alone program for a sanitizer build of the library's host code:
+ * feat_host_check.c -- the host side of the calls beside synthesis that runs
+ * without a device: argument checks, the snapshot sizes and the snapshot
+ * validation of include/lpcnet_mi355x.h's lpcnet_batch_*features*,
+ * _burg_cepstrum*, _plc_rows_device, _plc_update* and _encode* calls, in the
+ * order the contract gives them: value arguments, pointers, the null batch.
+ * `make hostcheck` builds it against the in-tree library and `make check`
+ * runs it.  It is also a stand-alone program for a sanitizer build of the
+ * library's host code:
  *
  *   make lib BUILD=build_san LIB=build_san/liblpcnet_mi355x.so \
  *        EXTRA="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer"
@@ -71,6 +75,71 @@ int main(void)
   const int good = 223;
   memcpy(st + n - 4, &good, 4);
   CHECK(lpcnet_batch_features_restore_state(NULL, 0, st) == -1 && err_has("null batch"));
+
+  /* Burg analysis: host calls, then the device call's col / row / nframes */
+  CHECK(lpcnet_batch_burg_cepstrum(NULL, pcm, feat, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum(NULL, NULL, feat, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum(NULL, pcm, NULL, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum_float(NULL, (const float *)feat, feat, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum_float(NULL, NULL, feat, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum_device(NULL, pcm, feat, 36, -1, NULL, 1) == -1 && err_has("col"));
+  static const int brows[][2] = {{0, 0}, {35, 0}, {-36, 0}, {36, 1}, {56, 21}};
+  for (size_t i = 0; i < sizeof(brows) / sizeof(brows[0]); i++)
+    CHECK(lpcnet_batch_burg_cepstrum_device(NULL, pcm, feat, brows[i][0], brows[i][1], NULL, 1) == -1 && err_has("row"));
+  CHECK(lpcnet_batch_burg_cepstrum_device(NULL, pcm, feat, 36, 0, NULL, -1) == -1 && err_has("nframes"));
+  CHECK(lpcnet_batch_burg_cepstrum_device(NULL, NULL, feat, 36, 0, NULL, 1) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum_device(NULL, pcm, NULL, 36, 0, NULL, 1) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum_device(NULL, pcm, feat, 36, 0, NULL, 1) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_burg_cepstrum_device(NULL, pcm, feat, 57, 21, NULL, 1) == -1 && err_has("null batch"));
+
+  /* the predictor's input rows: parts, then pointers, then the batch */
+  static const int parts[] = {0, 4, -1, 7};
+  for (size_t i = 0; i < sizeof(parts) / sizeof(parts[0]); i++)
+    CHECK(lpcnet_batch_plc_rows_device(NULL, pcm, feat, parts[i], 1.f, NULL) == -1 && err_has("parts"));
+  CHECK(lpcnet_batch_plc_rows_device(NULL, NULL, feat, 3, 1.f, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_plc_rows_device(NULL, pcm, NULL, 3, 1.f, NULL) == -1 && !err_has("null batch"));
+  for (int p = 1; p <= 3; p++) CHECK(lpcnet_batch_plc_rows_device(NULL, pcm, feat, p, 1.f, NULL) == -1 && err_has("null batch"));
+
+  /* the good-packet step asks for a batch with PLC records before anything else */
+  CHECK(lpcnet_batch_plc_update(NULL, pcm, feat, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_plc_update(NULL, NULL, NULL, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_plc_update_device(NULL, pcm, feat, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_plc_update_device(NULL, NULL, NULL, NULL) == -1 && err_has("null batch"));
+
+  /* 1.6 kb/s encoder */
+  unsigned char pk[8];
+  CHECK(lpcnet_batch_encode(NULL, pcm, pk, feat, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_encode(NULL, pcm, pk, NULL, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_encode(NULL, NULL, pk, feat, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_encode(NULL, pcm, NULL, feat, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_compute_features4(NULL, pcm, feat, NULL) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_compute_features4(NULL, NULL, feat, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_compute_features4(NULL, pcm, NULL, NULL) == -1 && !err_has("null batch"));
+  for (size_t i = 0; i < sizeof(rows) / sizeof(rows[0]); i++)
+    CHECK(lpcnet_batch_encode_device(NULL, pcm, pk, feat, rows[i], NULL, 1) == -1 && err_has("row"));
+  CHECK(lpcnet_batch_encode_device(NULL, pcm, pk, feat, 20, NULL, -1) == -1 && err_has("npackets"));
+  CHECK(lpcnet_batch_encode_device(NULL, NULL, pk, feat, 20, NULL, 1) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_encode_device(NULL, pcm, NULL, feat, 20, NULL, 1) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_encode_device(NULL, pcm, pk, NULL, 20, NULL, 1) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_encode_device(NULL, pcm, pk, feat, 36, NULL, 0) == -1 && err_has("null batch"));
+
+  /* the encoder snapshot: the features snapshot, then vq_mem[18] */
+  const int ne = lpcnet_batch_encode_state_size(NULL);
+  CHECK(ne == n + 18 * 4);
+  unsigned char *est = calloc((size_t)ne, 1);
+  if (!est) return 2;
+  CHECK(lpcnet_batch_encode_save_state(NULL, -1, est) == -1 && err_has("no such stream"));
+  CHECK(lpcnet_batch_encode_save_state(NULL, 0, NULL) == -1 && !err_has("null batch"));
+  CHECK(lpcnet_batch_encode_save_state(NULL, 0, est) == -1 && err_has("null batch"));
+  CHECK(lpcnet_batch_encode_restore_state(NULL, -1, est) == -1 && err_has("no such stream"));
+  CHECK(lpcnet_batch_encode_restore_state(NULL, 0, NULL) == -1 && !err_has("null batch"));
+  for (size_t i = 0; i < sizeof(bad) / sizeof(bad[0]); i++) {
+    memcpy(est + n - 4, &bad[i], 4);
+    CHECK(lpcnet_batch_encode_restore_state(NULL, 0, est) == -1 && err_has("best_i"));
+  }
+  memcpy(est + n - 4, &good, 4);
+  CHECK(lpcnet_batch_encode_restore_state(NULL, 0, est) == -1 && err_has("null batch"));
+  free(est);
 
   /* a batch cannot exist without a device: creation fails cleanly */
   if (lpcnet_mi355x_device_count() == 0) CHECK(lpcnet_batch_create(4, 0) == NULL);
