@@ -3,8 +3,8 @@
 #   make            -> lpcnet_amd/liblpcnet_mi355x.so + oracle/ libraries
 #   make lib        -> the product library only
 #   make check      -> builds and runs tools/model_host_check,
-#                      tools/pool_combiner_check and tools/feat_host_check
-#                      (CPU only)
+#                      tools/pool_combiner_check, tools/conceal_plan_check
+#                      and tools/feat_host_check (CPU only)
 #
 # Every translation unit is compiled with -ffp-contract=off: the engine is
 # bit-exact with the reference x86 build only without FMA contraction.
@@ -15,10 +15,10 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h $(CSRC)/conceal_plan.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/burg_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/burg_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o $(BUILD)/conceal_kernel.o $(BUILD)/conceal_calls.o $(BUILD)/conceal_plan.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
@@ -79,6 +79,11 @@ $(BUILD)/pool_combiner.o: $(CSRC)/pool_combiner.cpp $(CSRC)/pool_combiner.h | $(
 $(BUILD)/kernel_choice.o: $(CSRC)/kernel_choice.cpp $(CSRC)/kernel_choice.h | $(BUILD)
 	$(CXX) -O2 -fPIC -ffp-contract=off -std=c++17 -Iinclude -fvisibility=hidden -Wall -c $< -o $@
 
+# host-only: the concealment machine's planner (no device call, no HIP
+# include), system compiler
+$(BUILD)/conceal_plan.o: $(CSRC)/conceal_plan.cpp $(CSRC)/conceal_plan.h | $(BUILD)
+	$(CXX) -O2 -fPIC -ffp-contract=off -std=c++17 -Iinclude -fvisibility=hidden -Wall -c $< -o $@
+
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lpthread
 
@@ -99,6 +104,13 @@ POOLCHECK := tools/pool_combiner_check
 $(POOLCHECK): tools/pool_combiner_check.cpp $(BUILD)/pool_combiner.o $(CSRC)/pool_combiner.h
 	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $< $(BUILD)/pool_combiner.o -lpthread
 
+# stand-alone CPU check of the concealment planner over every loss pattern of
+# ten ticks (tools/conceal_plan_check.cpp gives the sanitizer recipe)
+PLANCHECK := tools/conceal_plan_check
+
+$(PLANCHECK): tools/conceal_plan_check.cpp $(BUILD)/conceal_plan.o $(CSRC)/conceal_plan.h
+	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $< $(BUILD)/conceal_plan.o
+
 # stand-alone check of what the side calls answer without a device, plain C
 # against the public header and the in-tree library
 # (tools/feat_host_check.c gives the sanitizer recipe)
@@ -107,18 +119,19 @@ FEATCHECK := tools/feat_host_check
 $(FEATCHECK): tools/feat_host_check.c include/lpcnet_mi355x.h $(LIB)
 	$(CC) -std=c99 -O2 -Wall -Wextra -Werror -Iinclude -o $@ $< -Llpcnet_amd -llpcnet_mi355x -Wl,-rpath,'$$ORIGIN/../lpcnet_amd'
 
-hostcheck: $(HOSTCHECK) $(POOLCHECK) $(FEATCHECK)
+hostcheck: $(HOSTCHECK) $(POOLCHECK) $(PLANCHECK) $(FEATCHECK)
 
 check: hostcheck
 	$(HOSTCHECK)
 	$(POOLCHECK)
+	$(PLANCHECK)
 	$(FEATCHECK)
 
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK) $(FEATCHECK)
+	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK) $(PLANCHECK) $(FEATCHECK)
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib synth dropin hostcheck oracle clean check

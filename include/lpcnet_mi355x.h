@@ -481,7 +481,8 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
  * inside lpcnet_plc_reset).
  * burg_cepstral_analysis and the predictor's input rows are the section
  * "Burg cepstral analysis" below.
- * Out of scope: the PLC state machine, process_multi_frame and drop-in
+ * The PLC state machine over these calls is the section "Concealment
+ * machine" below.  Out of scope: process_multi_frame and drop-in
  * LPCNetEncState handles (one stream per launch is slower than the CPU).
  * Argument errors return -1 with the reason in lpcnet_mi355x_last_error. */
 /* lpcnet_compute_single_frame_features for every stream s with active[s] != 0
@@ -518,8 +519,8 @@ LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream
  * (lpcnet_plc.c:205-258, 374-436) is a batch call: plc_rows assembles the
  * predictor's input row [36 Burg cepstrum | 20 features | flag] in device
  * memory, plc_update is rows + compute_plc_pred, the good-packet step.
- * Out of scope: the PLC state machine itself (pcm_fill loops, blending, DC
- * filter, FEC queue: per-stream host control flow over these batch calls),
+ * The PLC state machine itself (pcm_fill loops, blending, DC filter, FEC
+ * queue) is the section "Concealment machine" below.  Out of scope:
  * process_multi_frame and an fp32 predictor.
  * Argument errors return -1 with the reason in lpcnet_mi355x_last_error and
  * launch nothing. */
@@ -584,6 +585,70 @@ LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, 
  * kernel evaluates it.  Non-finite and non-positive inputs give 0, as the
  * x86 (int) cast does. */
 LPCNET_EXPORT int lpcnet_mi355x_enc_main_pitch(const float *center_pitch, int *out, int n);
+
+/* ---- Concealment machine (lpcnet_plc_update / lpcnet_plc_conceal) -----------
+ * lpcnet_plc.c:188-337, 495-503 for a whole batch, one call per 10 ms tick:
+ * every stream s has the semantics of one reference LPCNetPLCState (built, as
+ * the reference ships, with PLC_SKIP_UPDATES defined), bit-identical in the
+ * PCM of every tick and in its state to the same stream run alone.  Streams
+ * that received their packet and streams that lost it share the call.  The
+ * control state (pcm_fill, skip_analysis, blend, loss_count, the FEC queue's
+ * positions, the deferred-feature fill) depends on the sequence of lost and
+ * received ticks and FEC adds alone, so the host plans a tick for every stream
+ * without reading anything back; all of a tick's work is queued on the
+ * batch's stream and nothing synchronises between its steps.  The machine's
+ * per-stream data (st->features, st->pcm, dc_mem / syn_dc, plc_copy, the FEC
+ * queue, the deferred features) lives beside the synthesis state:
+ * lpcnet_batch_state_size and the snapshots are unchanged.  The synthesis,
+ * predictor and analysis state the machine advances are the batch's own
+ * (lpcnet_batch_save_state, _plc_save_state, _features_save_state see them).
+ * FEATURES_DELAY is the batch's at the time of the open; a tick after
+ * lpcnet_batch_set_model_constants changed it is refused (close and reopen).
+ * lpcnet_batch_load_model closes the machine.  lpcnet_batch_reset /
+ * _reset_stream also reset the machine's streams.
+ * Out of scope: the non-causal mode (lpcnet_plc.c:342-492), the #else
+ * branches of PLC_SKIP_UPDATES, an fp32 predictor, drop-in LPCNetPLCState
+ * handles.  Received frames on which burg_cepstral_analysis aborts in the
+ * reference (all-zero half-frames) are outside the contract, as above.
+ * Every refusal returns -1 with the reason in lpcnet_mi355x_last_error and
+ * launches nothing. */
+#define LPCNET_CONCEAL_CAUSAL    0 /* the values of the reference's LPCNET_PLC_*; LPCNET_PLC_NONCAUSAL (1) is refused */
+#define LPCNET_CONCEAL_CODEC     2
+#define LPCNET_CONCEAL_DC_FILTER 4
+/* lpcnet_plc_init + lpcnet_plc_reset for every stream (the synthesis,
+ * predictor and analysis states are reset too).  Needs a model with usable PLC
+ * records; one machine per batch. */
+LPCNET_EXPORT int lpcnet_batch_conceal_open(LPCNetBatch *b, int options);
+LPCNET_EXPORT int lpcnet_batch_conceal_close(LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_conceal_reset(LPCNetBatch *b, int stream /* lpcnet_plc_reset; -1: all */);
+/* One tick: stream s with lost[s] == 0 runs lpcnet_plc_update on pcm[s]
+ * (in/out), with lost[s] != 0 lpcnet_plc_conceal into pcm[s] (out);
+ * active[s] == 0 (NULL: all active): no tick for s, row and state untouched.
+ * pcm [B][160], lost [B]. */
+LPCNET_EXPORT int lpcnet_batch_conceal_frame(LPCNetBatch *b, short *pcm, const unsigned char *lost, const unsigned char *active);
+/* the same on device PCM [B][160], queued (lpcnet_batch_sync waits); lost and
+ * active are host memory, read during the call */
+LPCNET_EXPORT int lpcnet_batch_conceal_frame_device(LPCNetBatch *b, short *d_pcm, const unsigned char *lost,
+                                                    const unsigned char *active);
+/* lpcnet_plc_fec_add (features [20]; NULL: fec_skip++) and lpcnet_plc_fec_clear
+ * on one stream.  An add into a full queue with nothing to drop returns -1,
+ * "FEC buffer full", the state unchanged (the reference prints and returns). */
+LPCNET_EXPORT int lpcnet_batch_conceal_fec_add(LPCNetBatch *b, int stream, const float *features);
+LPCNET_EXPORT int lpcnet_batch_conceal_fec_clear(LPCNetBatch *b, int stream);
+/* tests / diagnostics, after a synchronisation: ctrl [9] = pcm_fill,
+ * skip_analysis, blend, loss_count, fec_fill_pos, fec_read_pos, fec_keep_pos,
+ * fec_skip, feature_buffer_fill; features [20] = st->features; pcm_buf
+ * [FEATURES_DELAY * 160 + 240] = st->pcm; dc [2] = dc_mem, syn_dc */
+LPCNET_EXPORT int lpcnet_batch_conceal_get_state(LPCNetBatch *b, int stream, int *ctrl, float *features, short *pcm_buf, double *dc);
+/* Host only: the machine's planner on one stream from reset over nticks ticks.
+ * lost [nticks]; fec_adds [nticks] (NULL: none): before tick t, n > 0 adds,
+ * -1 a NULL add, -2 a clear.  steps (NULL: count only) receives up to
+ * max_steps triples (op, a, b) -- the primitive calls of lpcnet_plc.c in order,
+ * see conceal_plan.h -- tick_end [nticks] (NULL: not wanted) the number of
+ * steps up to and including each tick, ctrl [nticks][9] (NULL: not wanted) the
+ * control fields after each tick.  Returns the number of steps. */
+LPCNET_EXPORT int lpcnet_mi355x_conceal_plan(int options, int features_delay, const unsigned char *lost, const int *fec_adds,
+                                             int nticks, int *steps, int max_steps, int *tick_end, int *ctrl);
 
 /* Last error string of this thread. */
 LPCNET_EXPORT const char *lpcnet_mi355x_last_error(void);

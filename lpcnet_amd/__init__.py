@@ -35,6 +35,11 @@ PLC_ROW_BURG = 1    # LPCNET_PLC_ROW_BURG
 PLC_ROW_FEATURES = 2  # LPCNET_PLC_ROW_FEATURES
 VARIANT_INT8 = 0
 VARIANT_FP32 = 1
+CONCEAL_CAUSAL = 0     # LPCNET_CONCEAL_*: the reference's LPCNET_PLC_* values
+CONCEAL_CODEC = 2
+CONCEAL_DC_FILTER = 4
+CONCEAL_CTRL = ("pcm_fill", "skip_analysis", "blend", "loss_count", "fec_fill_pos", "fec_read_pos", "fec_keep_pos",
+                "fec_skip", "feature_buffer_fill")
 
 
 class LPCNetError(RuntimeError):
@@ -157,6 +162,16 @@ def _load():
         "lpcnet_batch_encode_save_state": (i, [vp, i, vp]),
         "lpcnet_batch_encode_restore_state": (i, [vp, i, vp]),
         "lpcnet_mi355x_enc_main_pitch": (i, [vp, vp, i]),
+        # concealment machine (lpcnet_plc_update / lpcnet_plc_conceal)
+        "lpcnet_batch_conceal_open": (i, [vp, i]),
+        "lpcnet_batch_conceal_close": (i, [vp]),
+        "lpcnet_batch_conceal_reset": (i, [vp, i]),
+        "lpcnet_batch_conceal_frame": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_conceal_frame_device": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_conceal_fec_add": (i, [vp, i, vp]),
+        "lpcnet_batch_conceal_fec_clear": (i, [vp, i]),
+        "lpcnet_batch_conceal_get_state": (i, [vp, i, vp, vp, vp, vp]),
+        "lpcnet_mi355x_conceal_plan": (i, [i, i, vp, vp, i, vp, i, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -295,6 +310,34 @@ def enc_main_pitch(center_pitch: np.ndarray) -> np.ndarray:
     if lib.lpcnet_mi355x_enc_main_pitch(x.ctypes.data, out.ctypes.data, x.size) != 0:
         raise LPCNetError(last_error())
     return out
+
+
+def conceal_plan(options: int, features_delay: int, lost, fec_adds=None):
+    """The concealment machine's planner on one stream from reset (host only):
+    lost [nticks] (non-zero: the tick's packet is lost); fec_adds [nticks] or
+    None: before tick t, n > 0 FEC adds, -1 a NULL add, -2 a clear.  Returns
+    (steps, ctrl): per tick the list of (op, a, b) primitive calls of
+    lpcnet_plc.c in order (conceal_plan.h names them) and the control fields
+    after the tick as a dict keyed by CONCEAL_CTRL."""
+    lo = np.ascontiguousarray(np.asarray(lost) != 0, np.uint8)
+    n = lo.size
+    fa = None if fec_adds is None else np.ascontiguousarray(fec_adds, np.int32)
+    if fa is not None and fa.shape != (n,):
+        raise ValueError(f"fec_adds must be [{n}]")
+    end = np.zeros(max(n, 1), np.int32)
+    ctrl = np.zeros((max(n, 1), len(CONCEAL_CTRL)), np.int32)
+    total = lib.lpcnet_mi355x_conceal_plan(options, features_delay, _ptr(lo), _ptr(fa), n, None, 0, None, None)
+    if total < 0:
+        raise LPCNetError(last_error())
+    st = np.zeros((max(total, 1), 3), np.int32)
+    if lib.lpcnet_mi355x_conceal_plan(options, features_delay, _ptr(lo), _ptr(fa), n, st.ctypes.data, total,
+                                      end.ctypes.data, ctrl.ctypes.data) != total:
+        raise LPCNetError(last_error())
+    steps, first = [], 0
+    for t in range(n):
+        steps.append([tuple(int(v) for v in row) for row in st[first:end[t]]])
+        first = int(end[t])
+    return steps, [dict(zip(CONCEAL_CTRL, (int(v) for v in ctrl[t]))) for t in range(n)]
 
 
 def synthetic_features(stream: int, nframes: int) -> np.ndarray:
@@ -841,6 +884,72 @@ class LPCNetBatch:
     def encode_restore_state(self, stream: int, state: bytes) -> None:
         _restore_snapshot(lib.lpcnet_batch_encode_restore_state, self._b, stream, state,
                           lib.lpcnet_batch_encode_state_size(self._b), "encoder state of the wrong size")
+
+    # -- concealment machine (lpcnet_plc_update / lpcnet_plc_conceal) --------
+    def conceal_open(self, options: int = CONCEAL_CAUSAL) -> None:
+        """lpcnet_plc_init + lpcnet_plc_reset for every stream: CONCEAL_CAUSAL
+        or CONCEAL_CODEC, with or without CONCEAL_DC_FILTER.  Needs a model
+        with PLC records."""
+        if lib.lpcnet_batch_conceal_open(self._b, options) != 0:
+            raise LPCNetError(last_error())
+
+    def conceal_close(self) -> None:
+        if lib.lpcnet_batch_conceal_close(self._b) != 0:
+            raise LPCNetError(last_error())
+
+    def conceal_reset(self, stream: int | None = None) -> None:
+        """lpcnet_plc_reset of one stream (None: all)."""
+        if lib.lpcnet_batch_conceal_reset(self._b, -1 if stream is None else stream) != 0:
+            raise LPCNetError(last_error())
+
+    def _lost_arg(self, lost) -> np.ndarray:
+        lo = np.ascontiguousarray(np.asarray(lost) != 0, np.uint8)
+        if lo.shape != (self.B,):
+            raise ValueError(f"lost must be [{self.B}]")
+        return lo
+
+    def conceal_frame(self, pcm: np.ndarray, lost, active=None) -> np.ndarray:
+        """One tick: stream s with lost[s] == 0 runs lpcnet_plc_update on
+        pcm[s], with lost[s] != 0 lpcnet_plc_conceal into it.  pcm [B, 160]
+        int16; returns the PCM after the tick (rows of inactive streams as
+        given)."""
+        p = _pcm_arg(pcm, (self.B, FRAME_SIZE)).copy()
+        lo, a = self._lost_arg(lost), _active_arg(active, self.B)
+        if lib.lpcnet_batch_conceal_frame(self._b, _ptr(p), _ptr(lo), _ptr(a)) != 0:
+            raise LPCNetError(last_error())
+        return p
+
+    def conceal_frame_device(self, d_pcm: int, lost, active=None) -> None:
+        """conceal_frame on device PCM [B, 160] int16, in place and queued:
+        sync() waits.  lost / active are read during the call."""
+        lo, a = self._lost_arg(lost), _active_arg(active, self.B)
+        if lib.lpcnet_batch_conceal_frame_device(self._b, d_pcm, _ptr(lo), _ptr(a)) != 0:
+            raise LPCNetError(last_error())
+
+    def conceal_fec_add(self, stream: int, features: np.ndarray | None) -> None:
+        """lpcnet_plc_fec_add: features [>= 20], or None for a frame without FEC (fec_skip++)."""
+        f = None if features is None else np.ascontiguousarray(np.asarray(features, np.float32).ravel()[:NB_FEATURES])
+        if f is not None and f.size != NB_FEATURES:
+            raise ValueError("features must hold 20 values")
+        if lib.lpcnet_batch_conceal_fec_add(self._b, stream, _ptr(f)) != 0:
+            raise LPCNetError(last_error())
+
+    def conceal_fec_clear(self, stream: int) -> None:
+        if lib.lpcnet_batch_conceal_fec_clear(self._b, stream) != 0:
+            raise LPCNetError(last_error())
+
+    def conceal_state(self, stream: int) -> dict:
+        """The machine's state of one stream: the control fields (CONCEAL_CTRL),
+        features [20], pcm [FEATURES_DELAY * 160 + 240] int16, dc_mem, syn_dc."""
+        ctrl = np.zeros(len(CONCEAL_CTRL), np.int32)
+        f = np.zeros(NB_FEATURES, np.float32)
+        p = np.zeros(4 * FRAME_SIZE + 240, np.int16)  # the largest FEATURES_DELAY
+        dc = np.zeros(2, np.float64)
+        if lib.lpcnet_batch_conceal_get_state(self._b, stream, ctrl.ctypes.data, f.ctypes.data, p.ctypes.data, dc.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        out = dict(zip(CONCEAL_CTRL, (int(v) for v in ctrl)))
+        out.update(features=f, pcm=p[:self.info().features_delay * FRAME_SIZE + 240].copy(), dc_mem=float(dc[0]), syn_dc=float(dc[1]))
+        return out
 
     # -- device-resident path (benchmarks) ---------------------------------
     def device_alloc(self, nbytes: int) -> int:

@@ -1,15 +1,18 @@
 /*
  * batch.h -- what engine.cpp (the batch API), dropin.cpp (the drop-in
- * handles over it) and side_calls.cpp (the PLC, feature and LPC calls beside
- * synthesis) share: struct LPCNetBatch, the stream-state helpers, the timed
- * regions, the partial-batch steps a StatePool runs on its work batch and
- * what a batch's load and destruction call of side_calls.cpp.  Internal to
- * those three files.
+ * handles over it), side_calls.cpp (the PLC, feature and LPC calls beside
+ * synthesis) and conceal_calls.cpp (the concealment machine over all of them)
+ * share: struct LPCNetBatch, the stream-state helpers, the timed regions, the
+ * partial-batch steps a StatePool runs on its work batch and the machine on
+ * its work states, and what a batch's load, reset and destruction call of
+ * side_calls.cpp and conceal_calls.cpp.  Internal to those four files.
  */
 #ifndef LPCNET_BATCH_H
 #define LPCNET_BATCH_H
 
 #include <hip/hip_runtime.h>
+
+#include <string.h>
 
 #include <algorithm>
 #include <functional>
@@ -85,6 +88,40 @@ struct EncBufs {
   unsigned char *pk = nullptr; /* [B][8] */
   float *out = nullptr;        /* [4][B][NTF] */
 };
+
+/* One device allocation carved into 256-byte-aligned parts: add(p, n) plans n
+ * elements behind the pointer p; alloc() allocates the whole, sets every
+ * planned pointer and returns the base (null, the pointers untouched, when the
+ * device refuses). */
+class Carver {
+  struct Part {
+    void *ptr; /* the T * to set */
+    size_t off;
+  };
+  std::vector<Part> parts;
+  size_t bytes = 0;
+
+ public:
+  template <class T>
+  void add(T *&p, size_t n)
+  {
+    parts.push_back({&p, bytes});
+    bytes += (n * sizeof(T) + 255) & ~(size_t)255;
+  }
+  size_t size() const { return bytes; }
+  void *alloc()
+  {
+    char *base = nullptr;
+    if (hipMalloc(&base, bytes) != hipSuccess) return nullptr;
+    for (const Part &q : parts) {
+      char *p = base + q.off;
+      memcpy(q.ptr, &p, sizeof(p));
+    }
+    return base;
+  }
+};
+
+struct ConcealMachine; /* conceal_calls.cpp */
 
 /* ------------------------------------------------------------------------ */
 struct LPCNetBatch {
@@ -177,6 +214,8 @@ struct LPCNetBatch {
   FeatBufs feat{};
   BurgBufs burg{};
   EncBufs enc{};
+  /* the concealment machine (lpcnet_batch_conceal_open), null without one */
+  ConcealMachine *conceal = nullptr;
   /* diagnostics */
   unsigned long long *d_stamps = nullptr;
   /* timing */
@@ -242,6 +281,14 @@ int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm, int N
 int tail_first(LPCNetBatch *b, int nB, short *pcm, int N, int preload, const PreSync &pre = PreSync());
 int frame_first(LPCNetBatch *b, int nB, const float *features, bool keep_cond, const PreSync &pre = PreSync());
 int decode_first(LPCNetBatch *b, int nB, const unsigned char *packets, short *pcm, const PreSync &pre = PreSync());
+/* The device-I/O siblings of the three steps above: d_features [nB][NF] and
+ * d_pcm [nB][N] are device memory, everything is queued on b->stream and
+ * nothing is copied to or from the host or waited for.  They run on the nB
+ * states st points to (null: the batch's own first nB): the concealment
+ * machine's work states, gathered from and scattered to the batch's. */
+int synth_first_device(LPCNetBatch *b, int nB, const float *d_features, short *d_pcm, int N, int preload, StreamState *st = nullptr);
+int tail_first_device(LPCNetBatch *b, int nB, short *d_pcm, int N, int preload, StreamState *st = nullptr);
+int frame_first_device(LPCNetBatch *b, int nB, const float *d_features, bool keep_cond, StreamState *st = nullptr);
 
 /* side_calls.cpp.  plc_load: after a successful model load, with its blob's
  * records (optional: a blob without them loads as ever, plc_why says why the
@@ -256,6 +303,24 @@ void feat_free(LPCNetBatch *b);
  * caller synchronises. */
 enum { SIDE_PLC = 1, SIDE_FEAT = 2 };
 int side_reset(LPCNetBatch *b, int stream, int parts);
+/* the single launches of the side calls on b->stream, each a timed region
+ * (2 predictor, 3 extractor, 6 Burg analysis), and what they need ready:
+ * plc_ready (a model with usable PLC records; set_err otherwise), burg_ensure
+ * (the extractor's and the Burg tables and scratch) */
+int plc_ready(const LPCNetBatch *b);
+int burg_ensure(LPCNetBatch *b);
+int plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active);
+int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row, const unsigned char *d_active,
+                int stride = 0);
+int burg_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_out, int stride, int fill, float flag,
+                const unsigned char *d_active);
+
+/* conceal_calls.cpp.  conceal_free: close the batch's machine, if any (a model
+ * load, the batch's destruction).  conceal_reset_streams: queue on b->stream
+ * lpcnet_plc_reset's part beyond the synthesis, predictor and analysis state
+ * for one stream or all (stream < 0); nothing without a machine. */
+void conceal_free(LPCNetBatch *b);
+int conceal_reset_streams(LPCNetBatch *b, int stream);
 
 }  // namespace lpcnet_mi355x
 

@@ -646,6 +646,7 @@ LPCNET_EXPORT void lpcnet_batch_destroy(LPCNetBatch *b)
   b->set_device();
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->fstream) (void)hipStreamSynchronize(b->fstream);
+  conceal_free(b);
   free_model(b);
   plc_free(b);
   feat_free(b);
@@ -687,6 +688,7 @@ LPCNET_EXPORT int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *d
   if (!b) return -1;
   if (b->set_device()) return -1;
   (void)hipStreamSynchronize(b->stream);
+  conceal_free(b); /* its buffers are laid out for the model it was opened on */
   /* the batch's own copy of the blob, which its host model looks into */
   std::vector<unsigned char> blob;
   if (data && len > 0) blob.assign(data, data + len);
@@ -781,7 +783,7 @@ LPCNET_EXPORT int lpcnet_batch_reset_stream(LPCNetBatch *b, int stream)
   HIPCHK(hipMemcpyAsync(&b->d_state[stream], &s, sizeof(s), hipMemcpyHostToDevice, b->stream));
   /* lpcnet_plc_reset clears plc_net with the synthesis state, and the
    * analysis state (lpcnet_encoder_init inside lpcnet_plc_reset) */
-  if (side_reset(b, stream, SIDE_PLC | SIDE_FEAT)) return -1;
+  if (side_reset(b, stream, SIDE_PLC | SIDE_FEAT) || conceal_reset_streams(b, stream)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   b->min_fc = std::min(b->min_fc, s.frame_count);
   return 0;
@@ -795,6 +797,7 @@ LPCNET_EXPORT void lpcnet_batch_reset(LPCNetBatch *b)
   for (int i = 1; i < b->B; i++) v[i] = v[0];
   (void)hipMemcpyAsync(b->d_state, v.data(), sizeof(StreamState) * v.size(), hipMemcpyHostToDevice, b->stream);
   (void)side_reset(b, -1, SIDE_PLC | SIDE_FEAT);
+  (void)conceal_reset_streams(b, -1);
   (void)hipStreamSynchronize(b->stream);
   b->min_fc = v[0].frame_count;
 }
@@ -1122,7 +1125,7 @@ int lpcnet_mi355x::tail_first(LPCNetBatch *b, int nB, short *pcm, int N, int pre
   if (b->set_device()) return -1;
   if (ensure_trace(b, N)) return -1;
   if (preload > 0) HIPCHK(hipMemcpyAsync(b->d_pcm, pcm, sizeof(short) * N * nB, hipMemcpyHostToDevice, b->stream));
-  if (launch_frame_step(b, nullptr, nullptr, false, b->d_pcm, N, preload, -1, nB, false, false)) return -1;
+  if (tail_first_device(b, nB, b->d_pcm, N, preload)) return -1;
   if (pre && pre()) return -1;
   HIPCHK(hipMemcpyAsync(pcm, b->d_pcm, sizeof(short) * N * nB, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
@@ -1138,10 +1141,73 @@ int lpcnet_mi355x::frame_first(LPCNetBatch *b, int nB, const float *features, bo
   if (!features) { set_err("bad arguments"); return -1; }
   if (b->set_device()) return -1;
   HIPCHK(hipMemcpyAsync(b->d_feat, features, sizeof(float) * NF * nB, hipMemcpyHostToDevice, b->stream));
-  if (launch_frame_step(b, b->d_feat, b->d_lpc, true, nullptr, 0, 0, -1, nB, true, keep_cond)) return -1;
+  if (frame_first_device(b, nB, b->d_feat, keep_cond)) return -1;
   if (pre && pre()) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   return check_status(b);
+}
+
+/* ---- device-I/O siblings of the three steps above (batch.h) ----------------
+ * launch_frame_step on nB states with device buffers: queued on b->stream,
+ * no copy, no synchronisation, no look at the environment. */
+namespace {
+
+/* the states the launches of a step run on: the batch's own, or for the
+ * scope of this object the caller's work states.  The batch's frame_count
+ * bound is about its own states: a step on work states leaves it alone. */
+struct StepStates {
+  LPCNetBatch *b;
+  StreamState *own;
+  int min_fc;
+  bool work;
+  StepStates(LPCNetBatch *b_, StreamState *st) : b(b_), own(b_->d_state), min_fc(b_->min_fc), work(st != nullptr)
+  {
+    if (work) {
+      b->d_state = st;
+      b->min_fc = 0;
+    }
+  }
+  ~StepStates()
+  {
+    b->d_state = own;
+    if (work) b->min_fc = min_fc;
+  }
+};
+
+int step_ready(LPCNetBatch *b, int nB, int N, int preload, bool need_pcm, const void *d_pcm)
+{
+  if (!b || !b->have_model) { set_err("no model loaded"); return -1; }
+  if (nB < 1 || nB > b->B || N < 0 || N > FRAME || preload < 0 || (need_pcm && N > 0 && !d_pcm)) { set_err("bad arguments"); return -1; }
+  return b->set_device();
+}
+
+}  // namespace
+
+int lpcnet_mi355x::synth_first_device(LPCNetBatch *b, int nB, const float *d_features, short *d_pcm, int N, int preload,
+                                      StreamState *st)
+{
+  if (step_ready(b, nB, N, preload, true, d_pcm)) return -1;
+  if (!d_features) { set_err("bad arguments"); return -1; }
+  if (ensure_trace(b, N)) return -1;
+  StepStates on(b, st);
+  return launch_frame_step(b, d_features, b->d_lpc, true, d_pcm, N, preload, -1, nB);
+}
+
+int lpcnet_mi355x::tail_first_device(LPCNetBatch *b, int nB, short *d_pcm, int N, int preload, StreamState *st)
+{
+  if (step_ready(b, nB, N, preload, true, d_pcm)) return -1;
+  if (N == 0) return 0;
+  if (ensure_trace(b, N)) return -1;
+  StepStates on(b, st);
+  return launch_frame_step(b, nullptr, nullptr, false, d_pcm, N, preload, -1, nB, false, false);
+}
+
+int lpcnet_mi355x::frame_first_device(LPCNetBatch *b, int nB, const float *d_features, bool keep_cond, StreamState *st)
+{
+  if (step_ready(b, nB, 0, 0, false, nullptr)) return -1;
+  if (!d_features) { set_err("bad arguments"); return -1; }
+  StepStates on(b, st);
+  return launch_frame_step(b, d_features, b->d_lpc, true, nullptr, 0, 0, -1, nB, true, keep_cond);
 }
 
 extern "C" {

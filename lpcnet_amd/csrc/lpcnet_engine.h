@@ -591,6 +591,65 @@ __host__ __device__ inline int enc_main_pitch(const float *thr, float cp)
   return m;
 }
 
+/* The data side of lpcnet_plc_update / lpcnet_plc_conceal between their
+ * network and analysis calls (conceal_kernel.hip): per stream, beside
+ * StreamState (the synthesis snapshots keep their size), what of
+ * LPCNetPLCState (lpcnet_private.h:78-106) the causal modes carry, and the
+ * scratch a tick hands over through.  Every launcher takes the streams it
+ * works on as an index list idx [n] in device memory; a stream appears in a
+ * list at most once. */
+constexpr int CONCEAL_FEC_ROWS = 100; /* PLC_MAX_FEC */
+constexpr int CONCEAL_DEFER = 4;      /* MAX_FEATURE_BUFFER_SIZE */
+struct ConcealData {
+  int nstreams;
+  int delay;          /* FEATURES_DELAY the buffers were laid out for */
+  int buf;            /* PLC_BUF_SIZE = delay * FRAME + FRAME / 2 */
+  int nt;             /* n1 + n2 floats of one PLCNetState */
+  float *features;    /* [B][NF] st->features */
+  short *pcm;         /* [B][buf + FRAME] st->pcm */
+  double *dc;         /* [B][2] dc_mem, syn_dc */
+  float *copy;        /* [B][delay + 1][nt] plc_copy */
+  float *fec;         /* [B][CONCEAL_FEC_ROWS][NF] */
+  float *defer;       /* [B][CONCEAL_DEFER][NF] the LPCNetState's feature_buffer */
+  float *plc_state;   /* [B][nt] plc_net (the predictor's own state) */
+  /* scratch of one tick */
+  float *rows;        /* [B][PLC_IN] the predictor's input row */
+  short *lp;          /* [B][FRAME] lpcnet_plc_update_causal's lp */
+  int *delta;         /* [B] its delta; zero without the DC filter */
+  short *tmp;         /* [B][FRAME / 2] the speculative half frame */
+  const float *blend_w; /* [FRAME / 2] (float)(.5 - .5*cos(M_PI*i/80)), the host's cos */
+};
+enum { CONCEAL_DC_REMOVE = 0, CONCEAL_DC_RESTORE = 1, CONCEAL_DC_CONCEAL = 2 };
+/* the DC filter on io [B][FRAME] (lpcnet_plc.c:195-204, 283-287, 330-335): one lane per stream */
+int launch_conceal_dc(const ConcealData &d, const int *idx, int n, short *io, int mode, void *stream);
+/* io[0 .. 80) = blend of io and tmp - delta (:225-229) */
+int launch_conceal_blend(const ConcealData &d, const int *idx, int n, short *io, void *stream);
+/* features[0] = MAX16(-10, features[0] + att_table[.]) (:318-319) */
+int launch_conceal_attenuate(const ConcealData &d, const int *idx, int n, int loss_count, void *stream);
+/* st->pcm[dst_off .. + cnt) = (src_buf ? st->pcm : io row)[src_off .. + cnt); the ranges may overlap */
+int launch_conceal_move(const ConcealData &d, const int *idx, int n, const short *io, int dst_off, int src_buf, int src_off, int cnt,
+                        void *stream);
+/* plc_copy ring push (:305-306); plc_net = plc_copy[k] */
+int launch_conceal_plc_push(const ConcealData &d, const int *idx, int n, void *stream);
+int launch_conceal_plc_restore(const ConcealData &d, const int *idx, int n, int k, void *stream);
+/* fec[pos] into features and into the row's columns 36..55, flag -1, zeros before (:149-157) */
+int launch_conceal_fec_fetch(const ConcealData &d, const int *idx, int n, int pos, void *stream);
+/* run_frame_network_deferred's buffer push: analysed ? rows[36 .. 56) : features, `fill` frames held before */
+int launch_conceal_defer_push(const ConcealData &d, const int *idx, int n, int analysed, int fill, void *stream);
+/* work order [n][NF] / [n][N] from the streams' rows: w_feat (null: none) from
+ * features (defer_row < 0) or the deferred buffer's row; w_pcm (null: none)
+ * from st->pcm (src_buf) or the io row, at src_off */
+int launch_conceal_gather(const ConcealData &d, const int *idx, int n, float *w_feat, int defer_row, short *w_pcm, const short *io,
+                          int src_buf, int src_off, int N, void *stream);
+/* w_pcm [n][N] to the io rows at dst_off, or to tmp (io null) */
+int launch_conceal_scatter(const ConcealData &d, const int *idx, int n, const short *w_pcm, short *io, int dst_off, int N,
+                           void *stream);
+/* lpcnet_reset_signal (lpcnet.c:226-233) on st[idx[k]]; ulaw0 = lin2ulaw(0.f) */
+int launch_conceal_reset_signal(StreamState *st, const int *idx, int n, int ulaw0, void *stream);
+/* lpcnet_plc_fec_add's RNN_MOVE (:121) and RNN_COPY (:126) on one stream */
+int launch_conceal_fec_compact(const ConcealData &d, int s, int from, int rows, void *stream);
+int launch_conceal_fec_store(const ConcealData &d, int s, int pos, const float *features /* host, [NF] */, void *stream);
+
 }  // namespace lpcnet_mi355x
 
 #endif

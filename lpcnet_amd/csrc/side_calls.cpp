@@ -31,38 +31,6 @@ int copy_back_active(LPCNetBatch *b, const void *d_rows, size_t row, void *out, 
   return 0;
 }
 
-/* One device allocation carved into 256-byte-aligned parts: add(p, n) plans n
- * elements behind the pointer p; alloc() allocates the whole, sets every
- * planned pointer and returns the base (null, the pointers untouched, when the
- * device refuses). */
-class Carver {
-  struct Part {
-    void *ptr; /* the T * to set */
-    size_t off;
-  };
-  std::vector<Part> parts;
-  size_t bytes = 0;
-
- public:
-  template <class T>
-  void add(T *&p, size_t n)
-  {
-    parts.push_back({&p, bytes});
-    bytes += (n * sizeof(T) + 255) & ~(size_t)255;
-  }
-  size_t size() const { return bytes; }
-  void *alloc()
-  {
-    char *base = nullptr;
-    if (hipMalloc(&base, bytes) != hipSuccess) return nullptr;
-    for (const Part &q : parts) {
-      char *p = base + q.off;
-      memcpy(q.ptr, &p, sizeof(p));
-    }
-    return base;
-  }
-};
-
 }  // namespace
 
 /* ---- PLC prediction network (plc_kernel.hip) ------------------------------ */
@@ -141,7 +109,7 @@ int side_reset(LPCNetBatch *b, int stream, int parts)
 
 }  // namespace lpcnet_mi355x
 
-static int plc_ready(const LPCNetBatch *b)
+int lpcnet_mi355x::plc_ready(const LPCNetBatch *b)
 {
   if (!b) { set_err("null batch"); return -1; }
   if (!b->have_model) { set_err("no model loaded"); return -1; }
@@ -150,7 +118,7 @@ static int plc_ready(const LPCNetBatch *b)
 }
 
 /* one predictor launch on the batch's stream (timed as which = 2 when timing is on) */
-static int plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
+int lpcnet_mi355x::plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
 {
   PlcArgs a = b->pa;
   a.in = d_in;
@@ -296,8 +264,8 @@ static FeatArgs feat_args(const LPCNetBatch *b, const short *d_pcm, const float 
 }
 
 /* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
-static int feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
-                       const unsigned char *d_active, int stride = 0)
+int lpcnet_mi355x::feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
+                                const unsigned char *d_active, int stride)
 {
   /* stride 0: the dense [B][row] of every call but the predictor rows */
   const FeatArgs a = feat_args(b, d_pcm, d_pcm_f, d_features, row, stride ? stride : row, d_active);
@@ -410,7 +378,7 @@ static_assert(BURG_N == NTF, "the Burg calls stage their output in the extractor
 
 /* the extractor's tables and staging, and in one buffer the Burg table and
  * the scratch its three stages hand over through, on a batch's first Burg call */
-static int burg_ensure(LPCNetBatch *b)
+int lpcnet_mi355x::burg_ensure(LPCNetBatch *b)
 {
   if (feat_ensure(b)) return -1;
   if (b->burg.base) return 0;
@@ -434,8 +402,8 @@ static int burg_ensure(LPCNetBatch *b)
 }
 
 /* one Burg analysis (its three launches) on the batch's stream, timed as one region, which = 6, when timing is on */
-static int burg_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_out, int stride, int fill, float flag,
-                       const unsigned char *d_active)
+int lpcnet_mi355x::burg_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_out, int stride, int fill, float flag,
+                                const unsigned char *d_active)
 {
   BurgArgs a{};
   a.nstreams = b->B;
