@@ -1,11 +1,12 @@
 /*
- * batch.h -- what engine.cpp (the batch API), dropin.cpp (the drop-in
- * handles over it), side_calls.cpp (the PLC, feature and LPC calls beside
- * synthesis) and conceal_calls.cpp (the concealment machine over all of them)
- * share: struct LPCNetBatch, the stream-state helpers, the timed regions, the
- * partial-batch steps a StatePool runs on its work batch and the machine on
- * its work states, and what a batch's load, reset and destruction call of
- * side_calls.cpp and conceal_calls.cpp.  Internal to those four files.
+ * batch.h -- what engine.cpp (the batch), synth_steps.cpp (its synthesis and
+ * decode calls), dropin.cpp (the drop-in handles over them), side_calls.cpp
+ * (the PLC, feature and LPC calls beside synthesis) and conceal_calls.cpp (the
+ * concealment machine over all of them) share: struct LPCNetBatch, the
+ * stream-state helpers, the timed regions, the partial-batch steps a StatePool
+ * runs on its work batch and the machine on its work states, and what a
+ * batch's load, reset and destruction call of side_calls.cpp and
+ * conceal_calls.cpp.  Internal to those five files.
  */
 #ifndef LPCNET_BATCH_H
 #define LPCNET_BATCH_H
@@ -254,6 +255,12 @@ bool gru_state_plausible(const float *v, size_t n);
  * that is enc_kernel.hip, 6 Burg analysis); a null event: no pair. */
 int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e);
 void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames);
+/* engine.cpp.  ensure_trace: before the sample launches of a call of N samples
+ * per frame, the batch's trace buffers (allocated here) in b->sa, or none.
+ * check_status: after a sync of b->stream, report (set_err, -1) and clear a
+ * device-side abort. */
+int ensure_trace(LPCNetBatch *b, int N);
+int check_status(LPCNetBatch *b);
 
 /* One launch on b->stream as a timed region: with `on`, an event before and
  * one after it; with timing off no event is taken and nothing but the launch
@@ -274,7 +281,7 @@ int timed_launch(LPCNetBatch *b, int which, bool on, int frames, const char *fai
 }
 
 /* One step for the first nB streams of a batch, host I/O, `pre` queued
- * behind its kernels (engine.cpp, at each definition).  staged: the caller
+ * behind its kernels (synth_steps.cpp, at each definition).  staged: the caller
  * has queued the features / preload copies on b->stream already. */
 int synth_first(LPCNetBatch *b, int nB, const float *features, short *pcm, int N, int preload,
                 const PreSync &pre = PreSync(), bool staged = false);
@@ -285,7 +292,8 @@ int decode_first(LPCNetBatch *b, int nB, const unsigned char *packets, short *pc
  * d_pcm [nB][N] are device memory, everything is queued on b->stream and
  * nothing is copied to or from the host or waited for.  They run on the nB
  * states st points to (null: the batch's own first nB): the concealment
- * machine's work states, gathered from and scattered to the batch's. */
+ * machine's work states, gathered from and scattered to the batch's.  Only
+ * a frame network run on the batch's own states counts into min_fc. */
 int synth_first_device(LPCNetBatch *b, int nB, const float *d_features, short *d_pcm, int N, int preload, StreamState *st = nullptr);
 int tail_first_device(LPCNetBatch *b, int nB, short *d_pcm, int N, int preload, StreamState *st = nullptr);
 int frame_first_device(LPCNetBatch *b, int nB, const float *d_features, bool keep_cond, StreamState *st = nullptr);

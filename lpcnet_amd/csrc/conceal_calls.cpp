@@ -15,7 +15,7 @@
  * Burg launches of side_calls.cpp under the group's byte mask, and the
  * synthesis steps on work states: the group's StreamStates gathered into the
  * first n slots of a work array, the step run there (the *_first_device
- * steps of engine.cpp), the states scattered back -- or not, which is the
+ * steps of synth_steps.cpp), the states scattered back -- or not, which is the
  * reference's struct copy and restore around a speculative synthesis.
  * Nothing synchronises between the steps or at the end of the device form.
  *

@@ -1,8 +1,9 @@
 /*
  * dropin.cpp -- the drop-in single-stream API of include/lpcnet.h and the
  * lpcnet_mi355x_* handle and pool entry points over the batch engine
- * (engine.cpp, through batch.h): the handle registry and placement, the
- * StatePool of every (model, placement) with its slots and work batch, and
+ * (engine.cpp and synth_steps.cpp, through batch.h): the handle registry and
+ * placement, the StatePool of every (model, placement) with its slots and
+ * work batch, and
  * the 1.6 kb/s decoder handle.  Concurrent calls coalesce into one launch
  * through the pool's flat combiner (pool_combiner.cpp, host-only), which
  * calls pool_run here.

@@ -4,7 +4,8 @@
  * they look at comes in through their arguments (the environment as a
  * ChoiceEnv), so the rules can be checked without a device
  * (lpcnet_mi355x_kernel_choice, tests/test_kernel_choice.py).  No HIP
- * include; engine.cpp is the one caller of each.
+ * include; engine.cpp (the plan) and synth_steps.cpp (the launches and
+ * calls) are the callers.
  */
 #ifndef LPCNET_KERNEL_CHOICE_H
 #define LPCNET_KERNEL_CHOICE_H

@@ -353,3 +353,47 @@ def test_kernel_choice_does_not_matter(require_gpu):
     assert np.array_equal(outs[0], outs[1])
     fx = CR.fixture()
     assert np.array_equal(outs[0][:, 0], fx["causal_pcm"][1, :12]) and np.array_equal(outs[0][:, 1], fx["causal_pcm"][5, :12])
+
+
+# -- 9. steps on work states leave the batch's frame-count bound alone -----------------------------------
+
+def test_work_state_steps_keep_frame_count_bound(require_gpu):
+    """129 streams, the smallest batch on the chunked multi-frame path.  Five
+    of them lose packets in the first four ticks, so their synthesis runs on
+    the machine's work states and their frame_count advances; the others only
+    receive and stay at frame_count 0.  A synthesize_frames call of 8 frames
+    must then still start its multi-frame sample launch after the first
+    FEATURES_DELAY frames: a bound advanced by the work-state frames gives the
+    STATUS_ACTIVITY abort or other PCM than the per-frame path."""
+    import test_kernel_choice as KC
+    B, F = KC.OVERLAP_MAX_STREAMS + 1, 8
+    blob = CR.model_blob("causal")
+    plan, _, call, _ = KC.choice(L, blob, B, 0, 0, 0, [], [(F, 160, B, 0, 1, 0, 0, 0, 2, 0)])
+    assert plan[KC.PLAN.index("base")] in (1, 2, 3), "the model must plan a matrix-core sample kernel"
+    assert call[0] == 1 and call[2] == 1, "8 frames at 129 streams must take the chunked multi-frame path"
+    scripts = np.zeros(B, int)
+    lossy = {3: 4, 64: 2, 65: 4, 127: 2, 128: 4}  # stream: script; 4 loses ticks 0 and 1, 2 loses ticks 2 and 3
+    for s, sc in lossy.items():
+        scripts[s] = sc
+    feats = np.ascontiguousarray(np.stack([L.synthetic_features(s % 7, F)[:, :20] for s in range(B)], axis=1), np.float32)
+    outs = []
+    for chunking in (True, False):
+        b = open_batch(B)
+        b.set_frame_chunking(chunking)
+        d = Driver(b, scripts, True)
+        for _ in range(4):
+            d.tick()
+        fc = [b.get_state(s)["frame_count"] for s in range(B)]
+        assert all(fc[s] > 0 for s in lossy) and not any(fc[s] for s in range(B) if s not in lossy), fc
+        d_f, d_p = b.device_alloc(feats.nbytes), b.device_alloc(F * B * 160 * 2)
+        b.h2d(d_f, feats)
+        b.synthesize_frames(None, d_f, d_p, F, 160)
+        b.sync()
+        pcm = np.zeros((F, B, 160), np.int16)
+        b.d2h(pcm, d_p)
+        outs.append(pcm)
+        b.device_free(d_f)
+        b.device_free(d_p)
+        d.close()
+    assert outs[0].any()
+    assert np.array_equal(outs[0], outs[1])
