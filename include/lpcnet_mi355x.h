@@ -208,7 +208,10 @@ LPCNET_EXPORT int lpcnet_batch_memcpy_d2h(LPCNetBatch *b, void *dst, const void 
  * enc_kernel.hip (four frames per region), 6 the Burg analysis kernel
  * (lpcnet_batch_burg_cepstrum*, _plc_rows_device with the Burg part,
  * _plc_update*: one launch per frame, timed whenever enable > 0; the rows'
- * extractor launch counts under 3, the update's predictor under 2).  Returns
+ * extractor launch counts under 3, the update's predictor under 2), 8 the
+ * RDO-VAE encoder and 9 the RDO-VAE decoder (lpcnet_batch_rdovae_*, timed
+ * whenever enable > 0; a decode_all launch of n latents counts n frames).  7
+ * is no region: -1, as every value outside the list.  Returns
  * total ms and the number of launches.
  * enable: 0 off, 1 events around the sample kernel only, 2 (or more) around
  * both kernels. */
@@ -253,6 +256,12 @@ LPCNET_EXPORT int lpcnet_batch_get_state(LPCNetBatch *b, int stream, float *gru_
  * the reference's default shape (cond 128, two GRUs of 256 units,
  * lpcnet_plc.py:94-103), non-saturating; bits 3 and 4 = the same in a small
  * unequal shape (cond 64, 128 and 64 units); without bit3 the blob is
+ * unchanged; bit5 = append the DRED RDO-VAE's records
+ * (training_tf2/dump_rdovae.py), encoder and decoder, in the default shape
+ * (every stack layer 256 wide, T = 2048, gdense1 128, 80 latents, a 24-value
+ * state, conv kernel 4), non-saturating; bits 5 and 6 = the same in a small
+ * unequal shape (dense1/3/5 128 wide, the GRUs and dense7/8 64, T = 704,
+ * gdense1 64, 40 latents, a 32-value state); without bit5 the blob is
  * unchanged.
  * Returns the blob size; writes it if buf != NULL and cap is large enough. */
 LPCNET_EXPORT int lpcnet_mi355x_synthetic_model(unsigned seed, int variant, int flags, unsigned char *buf, int cap);
@@ -649,6 +658,75 @@ LPCNET_EXPORT int lpcnet_batch_conceal_get_state(LPCNetBatch *b, int stream, int
  * control fields after each tick.  Returns the number of steps. */
 LPCNET_EXPORT int lpcnet_mi355x_conceal_plan(int options, int features_delay, const unsigned char *lost, const int *fec_adds,
                                              int nticks, int *steps, int max_steps, int *tick_end, int *ctrl);
+
+/* ---- DRED RDO-VAE (dred_rdovae_enc.c, dred_rdovae_dec.c, dred_rdovae.c) -----
+ * The redundancy codec's networks for a whole batch, one launch per call
+ * (rdovae_kernel.hip), bit-identical per stream to the reference's x86
+ * DOT_PROD build.  The encoder turns two consecutive 20-feature frames (the
+ * earlier first) into L latents and an S-value initial state
+ * (dred_rdovae_encode_dframe); the decoder turns an initial state and
+ * latents back into feature frames, four per latent in the reference's
+ * reverse order (dec_init_states, decode_qframe, DRED_rdovae_decode_all).
+ * The records are optional in a blob and come from
+ * training_tf2/dump_rdovae.py: enc_dense1..8, bits_dense, gdense1, gdense2
+ * for the encoder, state1..3, dec_dense1..8, dec_final for the decoder; the
+ * two sides are independent, a blob may carry either, both or neither.
+ * Every dimension comes from the record sizes: GRU units and GRU input
+ * widths are multiples of 64 up to 512, every other layer has 1 to 512 rows,
+ * dec_final 80, the conv kernel size is 1 to 8.  A side whose records are
+ * missing, mis-sized, of unsupported dimensions, in an fp32 blob, or carry
+ * int8 weights in which a maddubs pair can saturate is refused: its calls
+ * return -1 with the reason in lpcnet_mi355x_last_error, and synthesis and
+ * every other call behave as ever.
+ * Each stream's encoder state (the three GRU states and the conv memory) and
+ * decoder state (the three GRU states) live in buffers of their own,
+ * allocated zeroed by the first of these calls; lpcnet_batch_reset does not
+ * touch them (lpcnet_reset knows nothing of DRED), lpcnet_batch_rdovae_reset
+ * zeroes them (DRED_rdovae_init_encoder / _decoder).
+ * Out of scope: the statistical model (dred_*_q8 / q10 / q15) and the entropy
+ * coding of latents, an fp32 RDO-VAE, emulating maddubs saturation, and
+ * writing decoded frames into the concealment machine's FEC queue on the
+ * device (reorder decode_all's output and use lpcnet_batch_conceal_fec_add). */
+/* dims[24]: encoder {L, S, T, conv kernel size, the eight stack widths,
+ * gdense1} at [0..12], decoder {L, S, T, the eight stack widths} at [13..23];
+ * zeros for a side without usable records; -1 (last_error: both reasons) only
+ * when neither side is usable.  Host only. */
+LPCNET_EXPORT int lpcnet_mi355x_rdovae_dims(const unsigned char *data, int len, int dims[24]);
+LPCNET_EXPORT int lpcnet_batch_rdovae_info(const LPCNetBatch *b, int dims[24]);
+/* dred_rdovae_encode_dframe for every stream s with active[s] != 0 (NULL:
+ * all): in [B][40] -> latents [B][L], initial_state [B][S]; rows of inactive
+ * streams are not written, their state does not move. */
+LPCNET_EXPORT int lpcnet_batch_rdovae_encode(LPCNetBatch *b, const float *in, float *latents, float *initial_state,
+                                             const unsigned char *active);
+/* the same on device buffers, queued on the batch's stream (lpcnet_batch_sync
+ * waits): d_features [2][B][row], row 20 or 36 -- what
+ * lpcnet_batch_compute_features_device writes for two frames; the first 20
+ * values of frame 0 and of frame 1 are the input */
+LPCNET_EXPORT int lpcnet_batch_rdovae_encode_device(LPCNetBatch *b, const float *d_features, int row, float *d_latents,
+                                                    float *d_state, const unsigned char *d_active);
+/* dred_rdovae_dec_init_states: state [B][S] -> the streams' decoder state */
+LPCNET_EXPORT int lpcnet_batch_rdovae_dec_init(LPCNetBatch *b, const float *state, const unsigned char *active);
+LPCNET_EXPORT int lpcnet_batch_rdovae_dec_init_device(LPCNetBatch *b, const float *d_state, const unsigned char *d_active);
+/* dred_rdovae_decode_qframe on the streams' decoder state: latents [B][L] ->
+ * qframe [B][80], four frames in reverse order */
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_qframe(LPCNetBatch *b, const float *latents, float *qframe, const unsigned char *active);
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_qframe_device(LPCNetBatch *b, const float *d_latents, float *d_qframe,
+                                                           const unsigned char *d_active);
+/* DRED_rdovae_decode_all: state [B][S], latents [B][n][L] -> features
+ * [B][4 n][20] in the reference's own order, on a temporary state -- the
+ * streams' decoder state is neither read nor written.  n == 0: nothing, 0. */
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_all(LPCNetBatch *b, const float *state, const float *latents, float *features, int n,
+                                                 const unsigned char *active);
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_all_device(LPCNetBatch *b, const float *d_state, const float *d_latents,
+                                                        float *d_features, int n, const unsigned char *d_active);
+/* which: 1 the encoder's state, 2 the decoder's, 3 both (the encoder's
+ * first).  reset: stream -1 is every stream.  A snapshot is the GRU states
+ * dense2 | dense4 | dense6 and, for the encoder, the conv memory
+ * [(kernel size - 1)][T], the oldest input first. */
+LPCNET_EXPORT int lpcnet_batch_rdovae_reset(LPCNetBatch *b, int stream, int which);
+LPCNET_EXPORT int lpcnet_batch_rdovae_state_size(const LPCNetBatch *b, int which);
+LPCNET_EXPORT int lpcnet_batch_rdovae_save_state(LPCNetBatch *b, int stream, int which, void *buf);
+LPCNET_EXPORT int lpcnet_batch_rdovae_restore_state(LPCNetBatch *b, int stream, int which, const void *buf);
 
 /* Last error string of this thread. */
 LPCNET_EXPORT const char *lpcnet_mi355x_last_error(void);

@@ -139,6 +139,21 @@ def _load():
         "lpcnet_batch_plc_state_size": (i, [vp]),
         "lpcnet_batch_plc_save_state": (i, [vp, i, vp]),
         "lpcnet_batch_plc_restore_state": (i, [vp, i, vp]),
+        # DRED RDO-VAE (dred_rdovae_enc.c, dred_rdovae_dec.c, dred_rdovae.c)
+        "lpcnet_mi355x_rdovae_dims": (i, [C.c_char_p, i, vp]),
+        "lpcnet_batch_rdovae_info": (i, [vp, vp]),
+        "lpcnet_batch_rdovae_encode": (i, [vp, vp, vp, vp, vp]),
+        "lpcnet_batch_rdovae_encode_device": (i, [vp, vp, i, vp, vp, vp]),
+        "lpcnet_batch_rdovae_dec_init": (i, [vp, vp, vp]),
+        "lpcnet_batch_rdovae_dec_init_device": (i, [vp, vp, vp]),
+        "lpcnet_batch_rdovae_decode_qframe": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_rdovae_decode_qframe_device": (i, [vp, vp, vp, vp]),
+        "lpcnet_batch_rdovae_decode_all": (i, [vp, vp, vp, vp, i, vp]),
+        "lpcnet_batch_rdovae_decode_all_device": (i, [vp, vp, vp, vp, i, vp]),
+        "lpcnet_batch_rdovae_reset": (i, [vp, i, i]),
+        "lpcnet_batch_rdovae_state_size": (i, [vp, i]),
+        "lpcnet_batch_rdovae_save_state": (i, [vp, i, i, vp]),
+        "lpcnet_batch_rdovae_restore_state": (i, [vp, i, i, vp]),
         # feature extraction (lpcnet_compute_single_frame_features)
         "lpcnet_batch_compute_features": (i, [vp, vp, vp, vp]),
         "lpcnet_batch_compute_features_float": (i, [vp, vp, vp, vp]),
@@ -245,16 +260,22 @@ def set_placement(devices) -> None:
 
 
 def synthetic_model(seed: int = 1, variant: int = VARIANT_INT8, saturating: bool = False, skewed: bool = False,
-                    codebooks: bool = False, plc: bool = False, plc_small: bool = False) -> bytes:
+                    codebooks: bool = False, plc: bool = False, plc_small: bool = False,
+                    rdovae: bool = False, rdovae_small: bool = False) -> bytes:
     """Deterministic synthetic default-size model in the reference blob format.
     skewed: GRU_A masks by a global per-gate threshold over skewed block
     energies (Sparsify, training_tf2/lpcnet.py:140-160): long block rows.
     codebooks: append the 1.6 kb/s decoder's ceps codebooks (other arrays unchanged).
     plc: append the PLC prediction network's records in the reference's default
     shape (cond 128, 256 / 256 units); plc_small: in a small unequal shape
-    (cond 64, 128 / 64 units) instead (other arrays unchanged)."""
+    (cond 64, 128 / 64 units) instead (other arrays unchanged).
+    rdovae: append the DRED RDO-VAE's encoder and decoder records in
+    dump_rdovae.py's default shape (stack 256 wide, T 2048, 80 latents, state
+    24); rdovae_small: in a small unequal shape (T 704, 40 latents, state 32)
+    instead (other arrays unchanged)."""
     flags = ((1 if saturating else 0) | (2 if skewed else 0) | (4 if codebooks else 0) |
-             (8 if plc or plc_small else 0) | (16 if plc_small else 0))
+             (8 if plc or plc_small else 0) | (16 if plc_small else 0) |
+             (32 if rdovae or rdovae_small else 0) | (64 if rdovae_small else 0))
     n = lib.lpcnet_mi355x_synthetic_model(seed, variant, flags, None, 0)
     buf = C.create_string_buffer(n)
     lib.lpcnet_mi355x_synthetic_model(seed, variant, flags, buf, n)
@@ -268,6 +289,25 @@ def plc_dims(blob: bytes) -> tuple[int, int, int, int]:
     if lib.lpcnet_mi355x_plc_dims(blob, len(blob), d) != 0:
         raise LPCNetError(last_error())
     return tuple(d)
+
+
+def _rdovae_dims_dict(d) -> dict:
+    """lpcnet_mi355x_rdovae_dims' 24 values as {"enc": {...} | None, "dec": {...} | None}."""
+    d = [int(v) for v in d]
+    enc = dict(L=d[0], S=d[1], T=d[2], kernel=d[3], widths=tuple(d[4:12]), gdense1=d[12]) if d[2] else None
+    dec = dict(L=d[13], S=d[14], T=d[15], widths=tuple(d[16:24])) if d[15] else None
+    return {"enc": enc, "dec": dec}
+
+
+def rdovae_dims(blob: bytes) -> dict:
+    """The dimensions of a blob's DRED RDO-VAE (host only): {"enc": dict(L, S,
+    T, kernel, widths, gdense1) or None, "dec": dict(L, S, T, widths) or
+    None}; a side without usable records is None.  Raises LPCNetError with
+    both reasons when neither side is usable."""
+    d = (C.c_int * 24)()
+    if lib.lpcnet_mi355x_rdovae_dims(blob, len(blob), d) != 0:
+        raise LPCNetError(last_error())
+    return _rdovae_dims_dict(d)
 
 
 def side_digest(blob: bytes | None) -> list[int]:
@@ -753,6 +793,121 @@ class LPCNetBatch:
         _restore_snapshot(lib.lpcnet_batch_plc_restore_state, self._b, stream, state, lib.lpcnet_batch_plc_state_size(self._b),
                           last_error() or "PLC state of the wrong size")  # the size call's error, when it left one
 
+    # -- DRED RDO-VAE (dred_rdovae_enc.c, dred_rdovae_dec.c, dred_rdovae.c) ----
+    def rdovae_info(self) -> dict:
+        """rdovae_dims of the loaded model."""
+        d = (C.c_int * 24)()
+        if lib.lpcnet_batch_rdovae_info(self._b, d) != 0:
+            raise LPCNetError(last_error())
+        return _rdovae_dims_dict(d)
+
+    def _rdovae_side(self, side: str) -> dict:
+        d = self.rdovae_info()[side]
+        if d is None:  # the reason is the size call's
+            lib.lpcnet_batch_rdovae_state_size(self._b, 1 if side == "enc" else 2)
+            raise LPCNetError(last_error())
+        return d
+
+    def rdovae_encode(self, inputs: np.ndarray, active: np.ndarray | None = None, latents: np.ndarray | None = None,
+                      state: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """dred_rdovae_encode_dframe on every stream with active[s] != 0 (None:
+        all): inputs [B, 40], two consecutive 20-feature frames, the earlier
+        first -> (latents [B, L], initial state [B, S]).  Rows of inactive
+        streams keep what ``latents`` / ``state`` held (zeros without them)."""
+        d = self._rdovae_side("enc")
+        x = np.ascontiguousarray(inputs, np.float32)
+        if x.shape != (self.B, 2 * NB_FEATURES):
+            raise ValueError(f"inputs must be [{self.B}, {2 * NB_FEATURES}]")
+        a = _active_arg(active, self.B)
+        z = _out_arg(latents, (self.B, d["L"]), what="latents")
+        st = _out_arg(state, (self.B, d["S"]), what="state")
+        if lib.lpcnet_batch_rdovae_encode(self._b, _ptr(x), _ptr(z), _ptr(st), _ptr(a)) != 0:
+            raise LPCNetError(last_error())
+        return z, st
+
+    def rdovae_encode_device(self, d_features: int | None, d_latents: int | None, d_state: int | None, row: int = NB_FEATURES,
+                             d_active: int | None = None) -> None:
+        """Enqueue the encoder on device buffers: d_features [2, B, row], row 20
+        or 36 (what compute_features_device writes for two frames), d_latents
+        [B, L], d_state [B, S].  sync() waits."""
+        if lib.lpcnet_batch_rdovae_encode_device(self._b, d_features, row, d_latents, d_state, d_active) != 0:
+            raise LPCNetError(last_error())
+
+    def rdovae_dec_init(self, state: np.ndarray, active: np.ndarray | None = None) -> None:
+        """dred_rdovae_dec_init_states: state [B, S] -> the streams' decoder state."""
+        d = self._rdovae_side("dec")
+        st = np.ascontiguousarray(state, np.float32)
+        if st.shape != (self.B, d["S"]):
+            raise ValueError(f"state must be [{self.B}, {d['S']}]")
+        a = _active_arg(active, self.B)
+        if lib.lpcnet_batch_rdovae_dec_init(self._b, _ptr(st), _ptr(a)) != 0:
+            raise LPCNetError(last_error())
+
+    def rdovae_dec_init_device(self, d_state: int | None, d_active: int | None = None) -> None:
+        if lib.lpcnet_batch_rdovae_dec_init_device(self._b, d_state, d_active) != 0:
+            raise LPCNetError(last_error())
+
+    def rdovae_decode_qframe(self, latents: np.ndarray, active: np.ndarray | None = None,
+                             out: np.ndarray | None = None) -> np.ndarray:
+        """dred_rdovae_decode_qframe on the streams' decoder state: latents
+        [B, L] -> [B, 80], four feature frames in reverse order."""
+        d = self._rdovae_side("dec")
+        z = np.ascontiguousarray(latents, np.float32)
+        if z.shape != (self.B, d["L"]):
+            raise ValueError(f"latents must be [{self.B}, {d['L']}]")
+        a = _active_arg(active, self.B)
+        o = _out_arg(out, (self.B, 4 * NB_FEATURES))
+        if lib.lpcnet_batch_rdovae_decode_qframe(self._b, _ptr(z), _ptr(o), _ptr(a)) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def rdovae_decode_qframe_device(self, d_latents: int | None, d_qframe: int | None, d_active: int | None = None) -> None:
+        if lib.lpcnet_batch_rdovae_decode_qframe_device(self._b, d_latents, d_qframe, d_active) != 0:
+            raise LPCNetError(last_error())
+
+    def rdovae_decode_all(self, state: np.ndarray, latents: np.ndarray, active: np.ndarray | None = None,
+                          out: np.ndarray | None = None) -> np.ndarray:
+        """DRED_rdovae_decode_all: state [B, S], latents [B, n, L] -> features
+        [B, 4 n, 20] in the reference's own order, on a temporary state (the
+        streams' decoder state is untouched)."""
+        d = self._rdovae_side("dec")
+        st = np.ascontiguousarray(state, np.float32)
+        z = np.ascontiguousarray(latents, np.float32)
+        if st.shape != (self.B, d["S"]):
+            raise ValueError(f"state must be [{self.B}, {d['S']}]")
+        if z.ndim != 3 or z.shape[0] != self.B or z.shape[2] != d["L"]:
+            raise ValueError(f"latents must be [{self.B}, n, {d['L']}]")
+        n = z.shape[1]
+        a = _active_arg(active, self.B)
+        o = _out_arg(out, (self.B, 4 * n, NB_FEATURES))
+        if lib.lpcnet_batch_rdovae_decode_all(self._b, _ptr(st), _ptr(z), _ptr(o), n, _ptr(a)) != 0:
+            raise LPCNetError(last_error())
+        return o
+
+    def rdovae_decode_all_device(self, d_state: int | None, d_latents: int | None, d_features: int | None, n: int,
+                                 d_active: int | None = None) -> None:
+        """Enqueue decode_all on device buffers: d_state [B, S], d_latents
+        [B, n, L], d_features [B, 4 n, 20].  sync() waits."""
+        if lib.lpcnet_batch_rdovae_decode_all_device(self._b, d_state, d_latents, d_features, n, d_active) != 0:
+            raise LPCNetError(last_error())
+
+    def rdovae_reset(self, stream: int | None = None, which: int = 3) -> None:
+        """Zero the RDO-VAE state of one stream (None: all): which = 1 the
+        encoder's, 2 the decoder's, 3 both."""
+        if lib.lpcnet_batch_rdovae_reset(self._b, -1 if stream is None else stream, which) != 0:
+            raise LPCNetError(last_error())
+
+    def rdovae_save_state(self, stream: int, which: int = 3) -> bytes:
+        """The GRU states dense2 | dense4 | dense6 and, for the encoder, the
+        conv memory of one stream (which as rdovae_reset; both: the encoder's first)."""
+        save = lambda b, s, buf: lib.lpcnet_batch_rdovae_save_state(b, s, which, buf)
+        return _save_snapshot(save, self._b, stream, lib.lpcnet_batch_rdovae_state_size(self._b, which))
+
+    def rdovae_restore_state(self, stream: int, state: bytes, which: int = 3) -> None:
+        restore = lambda b, s, buf: lib.lpcnet_batch_rdovae_restore_state(b, s, which, buf)
+        _restore_snapshot(restore, self._b, stream, state, lib.lpcnet_batch_rdovae_state_size(self._b, which),
+                          last_error() or "RDO-VAE state of the wrong size")  # the size call's error, when it left one
+
     # -- feature extraction (lpcnet_compute_single_frame_features) ----------
     def compute_features(self, pcm: np.ndarray, active: np.ndarray | None = None,
                          out: np.ndarray | None = None) -> np.ndarray:
@@ -988,7 +1143,8 @@ class LPCNetBatch:
     def kernel_ms(self, which: int = 0) -> tuple[float, int]:
         """(total ms, launches) of the timed launches since reset_timers: which = 0 sample
         kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor, 4 the 1.6 kb/s
-        encoder, 5 the part of 4 that is enc_kernel.hip, 6 the Burg analysis."""
+        encoder, 5 the part of 4 that is enc_kernel.hip, 6 the Burg analysis, 8 the
+        RDO-VAE encoder, 9 the RDO-VAE decoder (7 is no region)."""
         n = C.c_int(0)
         ms = lib.lpcnet_batch_kernel_ms(self._b, which, C.byref(n))
         return ms, n.value

@@ -38,7 +38,11 @@ using namespace lpcnet_mi355x;
     }                                                                                      \
   } while (0)
 
-constexpr int TIMED_REGIONS = 7; /* lpcnet_batch_kernel_ms's `which` */
+/* lpcnet_batch_kernel_ms's `which`: 0..6, then 8 and 9 for the RDO-VAE.  7 is
+ * no region and stays refused: callers probe it as the first invalid value. */
+constexpr int TIMED_REGIONS = 10;
+constexpr int TIMED_NONE = 7;
+constexpr int TIMED_RDOVAE_ENC = 8, TIMED_RDOVAE_DEC = 9;
 
 /* The device buffers of the calls beside synthesis (side_calls.cpp), one
  * value-initialised group per family: freeing a group is hipFree of what it
@@ -88,6 +92,23 @@ struct EncBufs {
   short *pcm = nullptr;        /* [4][B][FRAME] */
   unsigned char *pk = nullptr; /* [B][8] */
   float *out = nullptr;        /* [4][B][NTF] */
+};
+
+/* DRED RDO-VAE (rdovae_kernel.hip): the tables of each usable side, uploaded
+ * with the model into buffers of their own (rdovae_bufs: a re-plan of the
+ * synthesis tables keeps them), and what the first RDO-VAE call allocates in
+ * one zeroed buffer (rdovae_ensure): each stream's encoder state (the three
+ * GRU states, the conv memory) and decoder state (the three GRU states),
+ * decode_all's scratch state, the concatenation scratch and the host-I/O
+ * staging */
+struct RdovaeBufs {
+  void *base = nullptr;
+  float *enc_state = nullptr, *enc_mem = nullptr; /* [B][nt], [B][(ksize - 1) T] */
+  float *dec_state = nullptr, *dec_scratch = nullptr; /* [B][nt] */
+  float *cat = nullptr;                           /* [tiles][T max][PLC_TILE] */
+  float *in = nullptr, *lat = nullptr, *st = nullptr, *out = nullptr; /* staging */
+  size_t lat_cap = 0, out_cap = 0;                /* floats the staging of latents / output holds */
+  unsigned char *act = nullptr;
 };
 
 /* One device allocation carved into 256-byte-aligned parts: add(p, n) plans n
@@ -210,6 +231,13 @@ struct LPCNetBatch {
   std::string plc_why = "no model loaded"; /* why the PLC calls refuse this batch */
   PlcArgs pa{};
   std::vector<void *> plc_bufs;
+  /* DRED RDO-VAE: optional blob records, each side on its own */
+  bool rdo_ok[2] = {false, false}; /* encoder, decoder */
+  std::string rdo_why[2] = {"no model loaded", "no model loaded"};
+  RdovaeNet rdo_net[2] = {};
+  int rdo_dims[RDOVAE_DIMS] = {};
+  std::vector<void *> rdovae_bufs;
+  RdovaeBufs rdo{};
   /* the buffers of the calls beside synthesis */
   PlcBufs plc{};
   FeatBufs feat{};
@@ -222,7 +250,8 @@ struct LPCNetBatch {
   /* timing */
   int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
   std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
-  /* sample kernel, frame kernel, PLC predictor, feature extractor, encoder, the encoder's enc_kernel part, Burg analysis */
+  /* sample kernel, frame kernel, PLC predictor, feature extractor, encoder, the encoder's enc_kernel part, Burg analysis,
+   * none, RDO-VAE encoder, RDO-VAE decoder */
   std::vector<hipEvent_t> ev_pairs[TIMED_REGIONS];
   std::vector<int> ev_frames[TIMED_REGIONS];    /* frames covered by each pair */
   std::vector<hipEvent_t> ev_free;
@@ -305,6 +334,10 @@ int frame_first_device(LPCNetBatch *b, int nB, const float *d_features, bool kee
 void plc_load(LPCNetBatch *b, const std::vector<Arr> &L);
 void plc_free(LPCNetBatch *b);
 void feat_free(LPCNetBatch *b);
+/* rdovae_load, rdovae_free: the same for the RDO-VAE's tables and, freed
+ * only, its state and scratch (a new model has other dimensions) */
+void rdovae_load(LPCNetBatch *b, const std::vector<Arr> &L);
+void rdovae_free(LPCNetBatch *b);
 /* side_reset: queue on b->stream the zeroing of the side state the batch
  * holds, of one stream or of all (stream < 0): the predictor's GRU states
  * (SIDE_PLC), the analysis state and the encoder's vq_mem (SIDE_FEAT).  The

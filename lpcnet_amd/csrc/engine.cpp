@@ -288,7 +288,7 @@ int lpcnet_mi355x::ensure_trace(LPCNetBatch *b, int N)
  * to ev_taken from the moment it is taken, so a failing call leaks nothing.
  * timed: the pair (e0, e1) covers `frames` frames of region `which` (0 sample
  * kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor, 4 and 5 the
- * encoder, 6 the Burg analysis). */
+ * encoder, 6 the Burg analysis, 8 and 9 the RDO-VAE encoder and decoder). */
 int lpcnet_mi355x::mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e)
 {
   e = nullptr;
@@ -486,6 +486,7 @@ LPCNET_EXPORT void lpcnet_batch_destroy(LPCNetBatch *b)
   conceal_free(b);
   free_model(b);
   plc_free(b);
+  rdovae_free(b);
   feat_free(b);
   (void)hipFree(b->d_state);
   (void)hipFree(b->d_ck_sync);
@@ -535,9 +536,11 @@ LPCNET_EXPORT int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *d
     b->blob.swap(blob);
     b->host = std::move(host);
     plc_load(b, b->host->records); /* optional records: a blob without them loads as ever */
+    rdovae_load(b, b->host->records);
   } else if (!b->have_model) {
     plc_free(b);
     b->plc_why = "no model loaded";
+    rdovae_free(b);
   }
   return rc;
 }
@@ -744,7 +747,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
 
 LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *launches)
 {
-  if (!b || which < 0 || which >= TIMED_REGIONS) return -1;
+  if (!b || which < 0 || which >= TIMED_REGIONS || which == TIMED_NONE) return -1;
   b->set_device();
   (void)hipStreamSynchronize(b->stream);
   double tot = 0;
@@ -759,7 +762,7 @@ LPCNET_EXPORT double lpcnet_batch_kernel_ms(LPCNetBatch *b, int which, int *laun
 
 LPCNET_EXPORT int lpcnet_batch_kernel_frames(LPCNetBatch *b, int which)
 {
-  if (!b || which < 0 || which >= TIMED_REGIONS) return -1;
+  if (!b || which < 0 || which >= TIMED_REGIONS || which == TIMED_NONE) return -1;
   int n = 0;
   for (int k : b->ev_frames[which]) n += k;
   return n;

@@ -464,6 +464,63 @@ struct PlcArgs {
 int plc_lds_bytes(int cond, int n1, int n2);
 int launch_plc(const PlcArgs &a, void *stream);
 
+/* The DRED RDO-VAE (dred_rdovae_enc.c:38-95, dred_rdovae_dec.c:37-98,
+ * dred_rdovae.c:38-52) for a whole batch (rdovae_kernel.hip).  Encoder and
+ * decoder share one stack of eight layers -- dense (tanh), GRU, dense, GRU,
+ * dense, GRU, dense, dense -- whose outputs are concatenated into T floats;
+ * the encoder's heads are the causal conv bits_dense (linear, latents) and
+ * gdense1 -> gdense2 (tanh, the initial state), the decoder's the three state
+ * layers (tanh, the GRU states from an initial state) and dec_final (linear,
+ * four feature frames).  Dense weights are the blob's [in][out] floats, GRU
+ * weights the PLC's A tiles and seeds (PlcArgs).  A workgroup owns PLC_TILE
+ * streams. */
+constexpr int RDOVAE_DIM_MAX = 512;  /* every layer width, L, S and gdense1 */
+constexpr int RDOVAE_KSIZE_MAX = 8;  /* the conv's kernel size */
+constexpr int RDOVAE_QFRAME = 4 * NF; /* dec_final's rows */
+struct RdovaeDense {
+  const float *w, *b; /* [in][out], [out] */
+  int in, out;
+};
+struct RdovaeGru {
+  const uint4 *win, *wrec;
+  const int *seed;
+  int in, n;
+};
+struct RdovaeNet {
+  int in_dim;        /* 2 NF (encoder), L (decoder) */
+  int T, nt;         /* the concatenation; the three GRUs' units together */
+  int off[8];        /* each layer's offset in the concatenation */
+  RdovaeDense d[5];  /* stack layers 1, 3, 5, 7, 8 */
+  RdovaeGru g[3];    /* stack layers 2, 4, 6 */
+  /* encoder: bits_dense (in = ksize T), gdense1, gdense2; decoder: state1..3, dec_final */
+  RdovaeDense head[4];
+  int ksize;         /* encoder: the conv's kernel size */
+  int wmax;          /* the widest float row the kernel keeps in LDS */
+};
+struct RdovaeArgs {
+  RdovaeNet net;
+  int decoder;                 /* 0: one encoder call; 1: the decoder forms */
+  int nstreams;
+  const unsigned char *active; /* [B]; null: every stream */
+  float *state;                /* [B][nt] GRU states: the streams' own, or decode_all's scratch */
+  float *cat;                  /* [tiles][T][PLC_TILE] the concatenation, a scratch */
+  /* encoder: the input is in[s * in_stream + f * in_frame + 0..NF) of frames f = 0, 1 */
+  const float *in;
+  size_t in_stream, in_frame;
+  float *mem;                  /* [B][(ksize - 1) T] the conv's memory */
+  float *latents, *init_state; /* [B][L], [B][S] */
+  /* decoder: dec_init from d_init [B][S] when given, then nframes qframes:
+   * latent f of stream s at d_lat[(s * nframes + f) * L], its qframe at
+   * d_out[(s * nframes + f) * RDOVAE_QFRAME] */
+  const float *d_init, *d_lat;
+  float *d_out;
+  int nframes;
+  const uint32_t *rcp;
+  int rcp_hw;
+};
+int rdovae_lds_bytes(const RdovaeNet &n);
+int launch_rdovae(const RdovaeArgs &a, void *stream);
+
 /* The single-frame feature extractor (preemphasis, compute_frame_features,
  * process_single_frame: lpcnet_enc.c:872-880, 488-577, 814-870, pcount = 0)
  * for a whole batch (feat_kernel.hip).  What of LPCNetEncState crosses frames

@@ -363,6 +363,46 @@ extern "C" LPCNET_EXPORT int lpcnet_mi355x_synthetic_model(unsigned seed, int va
     ob[NB_FEATURES - 1] = 0.3f; /* the out[19] boost's clamp at .5 is met from both sides */
     blob.addf("plc_out_bias", ob);
   }
+  /* flags bit 5: the DRED RDO-VAE's records (dump_rdovae.py with
+   * keraslayerdump.py), encoder then decoder, from their own generator like
+   * the codebooks.  The default shape of dump_rdovae.py: every stack layer
+   * 256 wide (T = 2048), gdense1 128, 80 latents, a 24-value state, conv
+   * kernel 4; with bit 6 a small unequal shape: dense1/3/5 128 wide, the GRUs
+   * and dense7/8 64 (T = 704), gdense1 64, 40 latents, a 32-value state.
+   * GRUs as emit_plc_gru's (non-saturating, gate pre-activations O(1)); dense
+   * weights uniform with variance 1 / inputs, [in][out] as nnet.c reads them
+   * (the conv's [k T][L], oldest tap first). */
+  if (flags & 32) {
+    Rng v;
+    v.seed("lpcnet-mi355x-synthetic-rdovae", seed);
+    const bool small = (flags & 64) != 0;
+    const int wd = small ? 128 : 256, wg = small ? 64 : 256, g1 = small ? 64 : 128, lat = small ? 40 : 80,
+              sd = small ? 32 : 24, ks = 4, T = 3 * wd + 5 * wg;
+    auto dense = [&](const std::string &name, int in, int out, float gain = 1.f) {
+      blob.addf((name + "_weights").c_str(), uvec(v, (size_t)in * out, gain * sqrtf(3.f / in)));
+      blob.addf((name + "_bias").c_str(), uvec(v, out, 0.1f));
+    };
+    for (int dec = 0; dec < 2; dec++) {
+      const std::string pre = dec ? "dec_dense" : "enc_dense";
+      if (dec)
+        for (int k = 1; k <= 3; k++) dense("state" + std::to_string(k), sd, wg, 1.5f);
+      dense(pre + "1", dec ? lat : 2 * NB_FEATURES, wd);
+      emit_plc_gru(blob, v, pre + "2", wd, wg, variant);
+      dense(pre + "3", wg, wd, 2.f);
+      emit_plc_gru(blob, v, pre + "4", wd, wg, variant);
+      dense(pre + "5", wg, wd, 2.f);
+      emit_plc_gru(blob, v, pre + "6", wd, wg, variant);
+      dense(pre + "7", wg, wg, 2.f);
+      dense(pre + "8", wg, wg, 2.f);
+      if (dec) {
+        dense("dec_final", T, 4 * NB_FEATURES, 2.f);
+      } else {
+        dense("bits_dense", ks * T, lat, 2.f);
+        dense("gdense1", T, g1, 2.f);
+        dense("gdense2", g1, sd, 2.f);
+      }
+    }
+  }
   int size = (int)blob.data.size();
   if (buf && cap >= size) memcpy(buf, blob.data.data(), size);
   return size;

@@ -3,8 +3,9 @@
  * prediction network (lpcnet_batch_plc_*), the feature extractor
  * (lpcnet_batch_*features*), the Burg analysis, the predictor's input rows
  * and the good-packet step (lpcnet_batch_burg_cepstrum*, _plc_rows_device,
- * _plc_update*), the 1.6 kb/s encoder (lpcnet_batch_encode*) and the
- * stand-alone lpcnet_mi355x_device_lpc.
+ * _plc_update*), the 1.6 kb/s encoder (lpcnet_batch_encode*), the DRED
+ * RDO-VAE (lpcnet_batch_rdovae_*) and the stand-alone
+ * lpcnet_mi355x_device_lpc.
  * Their tables are built host-only in side_tables.cpp; the batch they run on
  * and its timed regions are engine.cpp's (batch.h).  Argument errors are
  * reported before any device call.
@@ -687,6 +688,362 @@ LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, 
   HIPCHK(hipMemcpy(b->enc.vq + (size_t)stream * NBANDS, (const char *)buf + sizeof(FeatState), NBANDS * 4, hipMemcpyHostToDevice));
   return 0;
 }
+
+}  // extern "C"
+
+/* ---- DRED RDO-VAE (rdovae_kernel.hip) -------------------------------------- */
+namespace lpcnet_mi355x {
+
+void rdovae_free(LPCNetBatch *b)
+{
+  for (void *p : b->rdovae_bufs) (void)hipFree(p);
+  b->rdovae_bufs.clear();
+  (void)hipFree(b->rdo.base);
+  b->rdo = {};
+  for (int k = 0; k < 2; k++) {
+    b->rdo_ok[k] = false;
+    b->rdo_why[k] = "no model loaded";
+    b->rdo_net[k] = RdovaeNet{};
+  }
+  std::fill(b->rdo_dims, b->rdo_dims + RDOVAE_DIMS, 0);
+}
+
+/* after a successful load_model, with its blob's records: the tables of each
+ * usable side; the state comes with the first call (rdovae_ensure) */
+void rdovae_load(LPCNetBatch *b, const std::vector<Arr> &L)
+{
+  rdovae_free(b);
+  RdovaeHost R;
+  (void)rdovae_parse(L, b->variant, R, true);
+  rdovae_dims_of(R, b->rdo_dims);
+  for (int k = 0; k < 2; k++) {
+    const RdovaeSide &S = k ? R.dec : R.enc;
+    b->rdo_why[k] = S.why;
+    if (!S.ok) continue;
+    RdovaeNet n;
+    bool ok = true;
+    for (const ModelUpload &u : rdovae_uploads(S, n)) {
+      void *p = nullptr;
+      if (!ok || hipMalloc(&p, u.bytes) != hipSuccess) { ok = false; break; }
+      b->rdovae_bufs.push_back(p);
+      if (hipMemcpy(p, u.src, u.bytes, hipMemcpyHostToDevice) != hipSuccess) ok = false;
+      memcpy(u.dst, &p, sizeof(p));
+    }
+    if (ok && rdovae_lds_bytes(n) > 160 * 1024) {
+      b->rdo_why[k] = "RDO-VAE: the layer widths need more LDS than a compute unit has";
+      continue;
+    }
+    if (!ok) {
+      b->rdo_why[k] = "RDO-VAE: device allocation or upload of the tables failed";
+      continue;
+    }
+    b->rdo_net[k] = n;
+    b->rdo_ok[k] = true;
+  }
+}
+
+}  // namespace lpcnet_mi355x
+
+enum { RDO_ENC = 0, RDO_DEC = 1 };
+
+/* a model with usable records of `side` (set_err otherwise) */
+static int rdovae_ready(const LPCNetBatch *b, int side)
+{
+  if (!b) { set_err("null batch"); return -1; }
+  if (!b->have_model) { set_err("no model loaded"); return -1; }
+  if (!b->rdo_ok[side]) { set_err(b->rdo_why[side].empty() ? "RDO-VAE: no usable records" : b->rdo_why[side]); return -1; }
+  return 0;
+}
+
+/* each stream's state (zero, as DRED_rdovae_init_encoder / _decoder leave
+ * it), the scratch and the staging of a batch, on its first RDO-VAE call */
+static int rdovae_ensure(LPCNetBatch *b)
+{
+  if (b->rdo.base) return 0;
+  const size_t B = (size_t)b->B, tiles = (B + PLC_TILE - 1) / PLC_TILE;
+  const RdovaeNet &E = b->rdo_net[RDO_ENC], &D = b->rdo_net[RDO_DEC];
+  const int *dm = b->rdo_dims;
+  RdovaeBufs r{};
+  Carver c;
+  if (b->rdo_ok[RDO_ENC]) {
+    c.add(r.enc_state, B * E.nt);
+    c.add(r.enc_mem, B * (size_t)(E.ksize - 1) * E.T + 1);
+  }
+  if (b->rdo_ok[RDO_DEC]) {
+    c.add(r.dec_state, B * D.nt);
+    c.add(r.dec_scratch, B * D.nt);
+  }
+  c.add(r.cat, tiles * (size_t)std::max(E.T, D.T) * PLC_TILE);
+  c.add(r.in, B * 2 * NF);
+  c.add(r.lat, B * (size_t)std::max(dm[0], dm[13]));
+  c.add(r.st, B * (size_t)std::max(dm[1], dm[14]));
+  c.add(r.out, B * RDOVAE_QFRAME);
+  c.add(r.act, B);
+  r.base = c.alloc();
+  if (!r.base || hipMemsetAsync(r.base, 0, c.size(), b->stream) != hipSuccess) { /* ordered before the first launch */
+    (void)hipFree(r.base);
+    set_err("RDO-VAE: device allocation failed");
+    return -1;
+  }
+  b->rdo = r;
+  return 0;
+}
+
+static RdovaeArgs rdovae_args(const LPCNetBatch *b, int side, const unsigned char *d_active)
+{
+  RdovaeArgs a{};
+  a.net = b->rdo_net[side];
+  a.decoder = side;
+  a.nstreams = b->B;
+  a.active = d_active;
+  a.cat = b->rdo.cat;
+  a.rcp = b->fa.rcp;
+  a.rcp_hw = b->sa.rcp_hw;
+  return a;
+}
+
+/* one encoder launch on the batch's stream (timed as which = 8 when timing is on) */
+static int rdovae_enc_launch(LPCNetBatch *b, const float *d_in, size_t in_stream, size_t in_frame, float *d_latents, float *d_state,
+                             const unsigned char *d_active)
+{
+  RdovaeArgs a = rdovae_args(b, RDO_ENC, d_active);
+  a.state = b->rdo.enc_state;
+  a.mem = b->rdo.enc_mem;
+  a.in = d_in;
+  a.in_stream = in_stream;
+  a.in_frame = in_frame;
+  a.latents = d_latents;
+  a.init_state = d_state;
+  return timed_launch(b, TIMED_RDOVAE_ENC, b->timing != 0, 1, "RDO-VAE encoder kernel launch failed",
+                      [&] { return launch_rdovae(a, b->stream); });
+}
+
+/* one decoder launch (which = 9): dec_init from d_init when given, then n
+ * qframes, on the streams' own state or, with `scratch`, on decode_all's */
+static int rdovae_dec_launch(LPCNetBatch *b, const float *d_init, const float *d_lat, float *d_out, int n, bool scratch,
+                             const unsigned char *d_active)
+{
+  RdovaeArgs a = rdovae_args(b, RDO_DEC, d_active);
+  a.state = scratch ? b->rdo.dec_scratch : b->rdo.dec_state;
+  a.d_init = d_init;
+  a.d_lat = d_lat;
+  a.d_out = d_out;
+  a.nframes = n;
+  return timed_launch(b, TIMED_RDOVAE_DEC, b->timing != 0, n, "RDO-VAE decoder kernel launch failed",
+                      [&] { return launch_rdovae(a, b->stream); });
+}
+
+/* the caller's rows and active mask into the staging, queued on b->stream */
+static int rdovae_stage(LPCNetBatch *b, void *d_dst, const void *src, size_t bytes, const unsigned char *active,
+                        const unsigned char *&d_active)
+{
+  if (src) HIPCHK(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, b->stream));
+  if (active) HIPCHK(hipMemcpyAsync(b->rdo.act, active, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
+  d_active = active ? b->rdo.act : nullptr;
+  return 0;
+}
+
+/* the floats of one stream's state: which = 1 the encoder's (GRU states, conv
+ * memory), 2 the decoder's, 3 both, the encoder's first; -1 (set_err) when a
+ * side that is asked for is not usable */
+static int rdovae_state_floats(const LPCNetBatch *b, int which, size_t part[3])
+{
+  if (which < 1 || which > 3) { set_err("RDO-VAE: which must be 1 (encoder), 2 (decoder) or 3 (both)"); return -1; }
+  part[0] = part[1] = part[2] = 0;
+  if ((which & 1) && rdovae_ready(b, RDO_ENC)) return -1;
+  if ((which & 2) && rdovae_ready(b, RDO_DEC)) return -1;
+  if (which & 1) {
+    part[0] = (size_t)b->rdo_net[RDO_ENC].nt;
+    part[1] = (size_t)(b->rdo_net[RDO_ENC].ksize - 1) * b->rdo_net[RDO_ENC].T;
+  }
+  if (which & 2) part[2] = (size_t)b->rdo_net[RDO_DEC].nt;
+  return 0;
+}
+
+extern "C" {
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_info(const LPCNetBatch *b, int dims[24])
+{
+  if (!b) { set_err("null batch"); return -1; }
+  if (!b->have_model) { set_err("no model loaded"); return -1; }
+  if (!b->rdo_ok[RDO_ENC] && !b->rdo_ok[RDO_DEC]) { set_err(b->rdo_why[RDO_ENC] + "; " + b->rdo_why[RDO_DEC]); return -1; }
+  if (!dims) { set_err("bad arguments"); return -1; }
+  std::copy(b->rdo_dims, b->rdo_dims + RDOVAE_DIMS, dims);
+  for (int k = 0; k < 2; k++) /* a side whose tables did not fit or upload */
+    if (!b->rdo_ok[k]) std::fill(dims + (k ? 13 : 0), dims + (k ? RDOVAE_DIMS : 13), 0);
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_encode_device(LPCNetBatch *b, const float *d_features, int row, float *d_latents,
+                                                    float *d_state, const unsigned char *d_active)
+{
+  if (row != NF && row != NTF) { set_err("RDO-VAE encode: row must be NB_FEATURES (20) or NB_TOTAL_FEATURES (36)"); return -1; }
+  if (rdovae_ready(b, RDO_ENC)) return -1;
+  if (!d_features || !d_latents || !d_state) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  return rdovae_enc_launch(b, d_features, (size_t)row, (size_t)b->B * row, d_latents, d_state, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_encode(LPCNetBatch *b, const float *in, float *latents, float *initial_state,
+                                             const unsigned char *active)
+{
+  if (rdovae_ready(b, RDO_ENC)) return -1;
+  if (!in || !latents || !initial_state) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  const unsigned char *d_act;
+  if (rdovae_stage(b, b->rdo.in, in, (size_t)b->B * 2 * NF * 4, active, d_act)) return -1;
+  if (rdovae_enc_launch(b, b->rdo.in, 2 * NF, NF, b->rdo.lat, b->rdo.st, d_act)) return -1;
+  if (copy_back_active(b, b->rdo.lat, (size_t)b->rdo_dims[0] * 4, latents, active)) return -1;
+  return copy_back_active(b, b->rdo.st, (size_t)b->rdo_dims[1] * 4, initial_state, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_dec_init_device(LPCNetBatch *b, const float *d_state, const unsigned char *d_active)
+{
+  if (rdovae_ready(b, RDO_DEC)) return -1;
+  if (!d_state) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  return rdovae_dec_launch(b, d_state, nullptr, nullptr, 0, false, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_dec_init(LPCNetBatch *b, const float *state, const unsigned char *active)
+{
+  if (rdovae_ready(b, RDO_DEC)) return -1;
+  if (!state) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  const unsigned char *d_act;
+  if (rdovae_stage(b, b->rdo.st, state, (size_t)b->B * b->rdo_dims[14] * 4, active, d_act)) return -1;
+  if (rdovae_dec_launch(b, b->rdo.st, nullptr, nullptr, 0, false, d_act)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_qframe_device(LPCNetBatch *b, const float *d_latents, float *d_qframe,
+                                                           const unsigned char *d_active)
+{
+  if (rdovae_ready(b, RDO_DEC)) return -1;
+  if (!d_latents || !d_qframe) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  return rdovae_dec_launch(b, nullptr, d_latents, d_qframe, 1, false, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_qframe(LPCNetBatch *b, const float *latents, float *qframe, const unsigned char *active)
+{
+  if (rdovae_ready(b, RDO_DEC)) return -1;
+  if (!latents || !qframe) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  const unsigned char *d_act;
+  if (rdovae_stage(b, b->rdo.lat, latents, (size_t)b->B * b->rdo_dims[13] * 4, active, d_act)) return -1;
+  if (rdovae_dec_launch(b, nullptr, b->rdo.lat, b->rdo.out, 1, false, d_act)) return -1;
+  return copy_back_active(b, b->rdo.out, RDOVAE_QFRAME * 4, qframe, active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_all_device(LPCNetBatch *b, const float *d_state, const float *d_latents,
+                                                        float *d_features, int n, const unsigned char *d_active)
+{
+  if (n < 0) { set_err("RDO-VAE decode_all: nb_latents < 0"); return -1; }
+  if (rdovae_ready(b, RDO_DEC)) return -1;
+  if (n == 0) return 0;
+  if (!d_state || !d_latents || !d_features) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  return rdovae_dec_launch(b, d_state, d_latents, d_features, n, true, d_active);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_decode_all(LPCNetBatch *b, const float *state, const float *latents, float *features, int n,
+                                                 const unsigned char *active)
+{
+  if (n < 0) { set_err("RDO-VAE decode_all: nb_latents < 0"); return -1; }
+  if (rdovae_ready(b, RDO_DEC)) return -1;
+  if (n == 0) return 0;
+  if (!state || !latents || !features) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  /* a packet's latents and frames: staging of this call's own size */
+  const size_t nl = (size_t)b->B * n * b->rdo_dims[13] * 4, no = (size_t)b->B * n * RDOVAE_QFRAME * 4;
+  float *d_lat = nullptr, *d_out = nullptr;
+  /* everything queued on b->stream; the buffers are freed behind a synchronisation */
+  auto run = [&]() -> int {
+    if (hipMalloc(&d_lat, nl) != hipSuccess || hipMalloc(&d_out, no) != hipSuccess) {
+      set_err("RDO-VAE decode_all: device allocation failed");
+      return -1;
+    }
+    const unsigned char *d_act;
+    if (rdovae_stage(b, b->rdo.st, state, (size_t)b->B * b->rdo_dims[14] * 4, active, d_act)) return -1;
+    HIPCHK(hipMemcpyAsync(d_lat, latents, nl, hipMemcpyHostToDevice, b->stream));
+    if (rdovae_dec_launch(b, b->rdo.st, d_lat, d_out, n, true, d_act)) return -1;
+    return copy_back_active(b, d_out, (size_t)n * RDOVAE_QFRAME * 4, features, active);
+  };
+  const int rc = run();
+  (void)hipStreamSynchronize(b->stream);
+  (void)hipFree(d_lat);
+  (void)hipFree(d_out);
+  return rc;
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_reset(LPCNetBatch *b, int stream, int which)
+{
+  size_t part[3];
+  if (rdovae_state_floats(b, which, part)) return -1;
+  if (stream < -1 || stream >= b->B) { set_err("no such stream"); return -1; }
+  if (!b->rdo.base) return 0; /* never used: a first use starts from the reset state */
+  if (b->set_device()) return -1;
+  const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)b->B : 1;
+  if (part[0]) HIPCHK(hipMemsetAsync(b->rdo.enc_state + first * part[0], 0, n * part[0] * 4, b->stream));
+  if (part[1]) HIPCHK(hipMemsetAsync(b->rdo.enc_mem + first * part[1], 0, n * part[1] * 4, b->stream));
+  if (part[2]) HIPCHK(hipMemsetAsync(b->rdo.dec_state + first * part[2], 0, n * part[2] * 4, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_state_size(const LPCNetBatch *b, int which)
+{
+  size_t part[3];
+  if (rdovae_state_floats(b, which, part)) return -1;
+  return (int)((part[0] + part[1] + part[2]) * 4);
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_save_state(LPCNetBatch *b, int stream, int which, void *buf)
+{
+  size_t part[3];
+  if (rdovae_state_floats(b, which, part)) return -1;
+  if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  const float *src[3] = {b->rdo.enc_state, b->rdo.enc_mem, b->rdo.dec_state};
+  char *out = (char *)buf;
+  for (int k = 0; k < 3; k++) {
+    if (!part[k]) continue;
+    HIPCHK(hipMemcpy(out, src[k] + (size_t)stream * part[k], part[k] * 4, hipMemcpyDeviceToHost));
+    out += part[k] * 4;
+  }
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_rdovae_restore_state(LPCNetBatch *b, int stream, int which, const void *buf)
+{
+  size_t part[3];
+  if (rdovae_state_floats(b, which, part)) return -1;
+  if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
+  /* the GRU states are what a recurrence of this engine leaves; the conv memory is any floats */
+  std::vector<float> v(part[0] + part[1] + part[2]);
+  memcpy(v.data(), buf, v.size() * 4);
+  if (!gru_state_plausible(v.data(), part[0]) || !gru_state_plausible(v.data() + part[0] + part[1], part[2])) {
+    set_err("RDO-VAE snapshot GRU state outside [-2, 2]: not a state this engine produced");
+    return -1;
+  }
+  if (b->set_device() || rdovae_ensure(b)) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  float *dst[3] = {b->rdo.enc_state, b->rdo.enc_mem, b->rdo.dec_state};
+  const float *in = v.data();
+  for (int k = 0; k < 3; k++) {
+    if (!part[k]) continue;
+    HIPCHK(hipMemcpy(dst[k] + (size_t)stream * part[k], in, part[k] * 4, hipMemcpyHostToDevice));
+    in += part[k];
+  }
+  return 0;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 /* ---- lpc_from_cepstrum on its own (lpc_kernel.hip) ------------------------ */
 LPCNET_EXPORT int lpcnet_mi355x_device_lpc(int device, const float *cepstra, float *lpc, int n)

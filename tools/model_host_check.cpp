@@ -31,7 +31,9 @@
  * and recurrent v_mfma_i32_16x16x64_i8 A tiles of both GRUs into dense
  * [3 n][K] matrices that must equal the ones assembled from the blob's index,
  * weight and recurrent-weight records, and recomputes every seed from subias
- * and the decoded rows' sums.
+ * and the decoded rows' sums.  The six GRUs of the synthetic RDO-VAEs
+ * (rdovae_parse; the default shape and the small one) go through the same
+ * check, after the dimensions derived from the record sizes.
  *
  * Under AddressSanitizer and UBSan (host code only):
  *
@@ -352,10 +354,62 @@ static bool decode_plc_tiles(const std::vector<uint4> &tiles, int n, int K, std:
   return true;
 }
 
-/* The PLC predictor of a synthetic blob: the input and recurrent A tiles of
- * both GRUs decode to the matrices assembled from the blob's _weights_idx /
- * _weights / _recurrent_weights records (as check_gru_b assembles GRU_B's),
- * and every seed is rne(subias * 128 * 127) + 128 * the decoded row's sum. */
+/* One compute_gruB layer `nm` of nin inputs and n units: its input and
+ * recurrent A tiles decode to the matrices assembled from the blob's
+ * _weights_idx / _weights / _recurrent_weights records (as check_gru_b
+ * assembles GRU_B's), and every seed is rne(subias * 128 * 127) + 128 * the
+ * decoded row's sum. */
+static bool check_gru_tiles(const std::vector<Arr> &L, const char *name, const std::string &nm, int nin, int n,
+                            const std::vector<uint4> &g_in, const std::vector<uint4> &g_rec, const std::vector<int> &seed)
+{
+  char tag[80];
+  snprintf(tag, sizeof tag, "%s/%s", name, nm.c_str());
+  std::vector<std::vector<int>> blocks;
+  const Arr *w = find(L, (nm + "_weights").c_str()), *r = find(L, (nm + "_recurrent_weights").c_str());
+  const Arr *sb = find(L, (nm + "_subias").c_str());
+  if (!parse_idx(L, (nm + "_weights_idx").c_str(), nin, 3 * n, blocks) || !w || !r || !sb || sb->size != 24 * n ||
+      w->size != 32 * total_blocks(blocks) || r->size != 3 * n * n) {
+    CHECK(false, "%s: records", tag);
+    return false;
+  }
+  std::vector<int> Rin((size_t)3 * n * nin, 0), Rrec((size_t)3 * n * n, 0), Din, Drec;
+  const int8_t *wb = (const int8_t *)w->data, *wr = (const int8_t *)r->data;
+  int t = 0;
+  for (int rb = 0; rb < 3 * n / 8; rb++)
+    for (int pos : blocks[rb]) {
+      for (int i = 0; i < 8; i++)
+        for (int c = 0; c < 4; c++) Rin[(size_t)(rb * 8 + i) * nin + pos + c] += wb[32 * t + 4 * i + c];
+      t++;
+    }
+  for (int rb = 0; rb < 3 * n / 8; rb++)
+    for (int cb = 0; cb < n / 4; cb++)
+      for (int i = 0; i < 8; i++)
+        for (int c = 0; c < 4; c++) Rrec[(size_t)(rb * 8 + i) * n + 4 * cb + c] = wr[32 * ((size_t)rb * (n / 4) + cb) + 4 * i + c];
+  if (!decode_plc_tiles(g_in, n, nin, Din, tag) || !decode_plc_tiles(g_rec, n, n, Drec, tag)) return false;
+  CHECK(Din == Rin, "%s: input tiles differ from the blob", tag);
+  CHECK(Drec == Rrec, "%s: recurrent tiles differ from the blob", tag);
+  CHECK(seed.size() == (size_t)6 * n, "%s: %zu seeds", tag, seed.size());
+  if (seed.size() != (size_t)6 * n) return false;
+  const float *subias = (const float *)sb->data;
+  for (int half = 0; half < 2; half++) {
+    const std::vector<int> &D = half ? Drec : Din;
+    const int K = half ? n : nin;
+    for (int row = 0; row < 3 * n; row++) {
+      int sum = 0;
+      for (int j = 0; j < K; j++) sum += D[(size_t)row * K + j];
+      /* _mm256_cvtps_epi32: round to nearest even; the synthetic subias stay far inside the int range */
+      const float v = subias[half * 3 * n + row] * (128.f * 127.f);
+      CHECK(fabsf(v) < 2147483648.f, "%s: subias %d of half %d out of range", tag, row, half);
+      if (!(fabsf(v) < 2147483648.f)) continue;
+      const int want = (int)((uint32_t)(int)nearbyintf(v) + (uint32_t)(128 * sum));
+      CHECK(seed[half * 3 * n + row] == want, "%s: seed %d of half %d is %d, recomputed %d", tag, row, half,
+            seed[half * 3 * n + row], want);
+    }
+  }
+  return true;
+}
+
+/* The PLC predictor of a synthetic blob: both GRUs under check_gru_tiles. */
 static void check_plc(const char *name, int flags, int cond, int n1, int n2)
 {
   const int len = lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, flags, nullptr, 0);
@@ -370,55 +424,42 @@ static void check_plc(const char *name, int flags, int cond, int n1, int n2)
   CHECK(P.cond == cond && P.n[0] == n1 && P.n[1] == n2, "%s: dims %d %d %d", name, P.cond, P.n[0], P.n[1]);
   int nin = P.cond;
   for (int k = 0; k < 2; k++) {
-    const int n = P.n[k];
-    const std::string nm = k ? "plc_gru2" : "plc_gru1";
-    char tag[80];
-    snprintf(tag, sizeof tag, "%s/%s", name, nm.c_str());
-    std::vector<std::vector<int>> blocks;
-    const Arr *w = find(L, (nm + "_weights").c_str()), *r = find(L, (nm + "_recurrent_weights").c_str());
-    const Arr *sb = find(L, (nm + "_subias").c_str());
-    if (!parse_idx(L, (nm + "_weights_idx").c_str(), nin, 3 * n, blocks) || !w || !r || !sb || sb->size != 24 * n ||
-        w->size != 32 * total_blocks(blocks) || r->size != 3 * n * n) {
-      CHECK(false, "%s: records", tag);
-      return;
-    }
-    std::vector<int> Rin((size_t)3 * n * nin, 0), Rrec((size_t)3 * n * n, 0), Din, Drec;
-    const int8_t *wb = (const int8_t *)w->data, *wr = (const int8_t *)r->data;
-    int t = 0;
-    for (int rb = 0; rb < 3 * n / 8; rb++)
-      for (int pos : blocks[rb]) {
-        for (int i = 0; i < 8; i++)
-          for (int c = 0; c < 4; c++) Rin[(size_t)(rb * 8 + i) * nin + pos + c] += wb[32 * t + 4 * i + c];
-        t++;
-      }
-    for (int rb = 0; rb < 3 * n / 8; rb++)
-      for (int cb = 0; cb < n / 4; cb++)
-        for (int i = 0; i < 8; i++)
-          for (int c = 0; c < 4; c++) Rrec[(size_t)(rb * 8 + i) * n + 4 * cb + c] = wr[32 * ((size_t)rb * (n / 4) + cb) + 4 * i + c];
-    if (!decode_plc_tiles(P.g_in[k], n, nin, Din, tag) || !decode_plc_tiles(P.g_rec[k], n, n, Drec, tag)) return;
-    CHECK(Din == Rin, "%s: input tiles differ from the blob", tag);
-    CHECK(Drec == Rrec, "%s: recurrent tiles differ from the blob", tag);
-    CHECK(P.seed[k].size() == (size_t)6 * n, "%s: %zu seeds", tag, P.seed[k].size());
-    if (P.seed[k].size() != (size_t)6 * n) return;
-    const float *subias = (const float *)sb->data;
-    for (int half = 0; half < 2; half++) {
-      const std::vector<int> &D = half ? Drec : Din;
-      const int K = half ? n : nin;
-      for (int row = 0; row < 3 * n; row++) {
-        int sum = 0;
-        for (int j = 0; j < K; j++) sum += D[(size_t)row * K + j];
-        /* _mm256_cvtps_epi32: round to nearest even; the synthetic subias stay far inside the int range */
-        const float v = subias[half * 3 * n + row] * (128.f * 127.f);
-        CHECK(fabsf(v) < 2147483648.f, "%s: subias %d of half %d out of range", tag, row, half);
-        if (!(fabsf(v) < 2147483648.f)) continue;
-        const int want = (int)((uint32_t)(int)nearbyintf(v) + (uint32_t)(128 * sum));
-        CHECK(P.seed[k][half * 3 * n + row] == want, "%s: seed %d of half %d is %d, recomputed %d", tag, row, half,
-              P.seed[k][half * 3 * n + row], want);
-      }
-    }
-    nin = n;
+    if (!check_gru_tiles(L, name, k ? "plc_gru2" : "plc_gru1", nin, P.n[k], P.g_in[k], P.g_rec[k], P.seed[k])) return;
+    nin = P.n[k];
   }
   plc_decoded++;
+}
+
+static int rdovae_decoded;
+
+/* The RDO-VAE of a synthetic blob: the dimensions from the record sizes and
+ * the six GRUs under check_gru_tiles. */
+static void check_rdovae(const char *name, int flags, int T, int lat, int sd, int g1)
+{
+  const int len = lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, flags, nullptr, 0);
+  std::vector<unsigned char> blob(len);
+  lpcnet_mi355x_synthetic_model(1, LPCNET_VARIANT_INT8, flags, blob.data(), len);
+  std::vector<Arr> L;
+  RdovaeHost R;
+  if (!parse_blob(L, blob.data(), len) || rdovae_parse(L, LPCNET_VARIANT_INT8, R, true) || !R.enc.ok || !R.dec.ok) {
+    CHECK(false, "%s: RDO-VAE records do not parse (%s)", name, last_err().c_str());
+    return;
+  }
+  int dims[RDOVAE_DIMS];
+  rdovae_dims_of(R, dims);
+  CHECK(dims[0] == lat && dims[1] == sd && dims[2] == T && dims[3] == 4 && dims[12] == g1, "%s: encoder dims %d %d %d %d %d", name,
+        dims[0], dims[1], dims[2], dims[3], dims[12]);
+  CHECK(dims[13] == lat && dims[14] == sd && dims[15] == T, "%s: decoder dims %d %d %d", name, dims[13], dims[14], dims[15]);
+  for (int dec = 0; dec < 2; dec++) {
+    const RdovaeSide &S = dec ? R.dec : R.enc;
+    for (int k = 0; k < 3; k++) {
+      const RdovaeGruHost &G = S.g[k];
+      const std::string nm = std::string(dec ? "dec_dense" : "enc_dense") + std::to_string(2 * k + 2);
+      CHECK(G.in == S.width[2 * k] && G.n == S.width[2 * k + 1], "%s/%s: %d -> %d", name, nm.c_str(), G.in, G.n);
+      if (!check_gru_tiles(L, name, nm, G.in, G.n, G.win, G.wrec, G.seed)) return;
+    }
+  }
+  rdovae_decoded++;
 }
 
 static bool read_file(const char *path, std::vector<unsigned char> &out)
@@ -466,13 +507,16 @@ int main(int argc, char **argv)
     /* synthetic-model flags 8: PLC records in the default shape, 8 | 16: in the small one */
     check_plc("plc", 8, 128, 256, 256);
     check_plc("plc_small", 8 | 16, 64, 128, 64);
+    /* flags 32: RDO-VAE records in the default shape, 32 | 64: in the small one */
+    check_rdovae("rdovae", 32, 2048, 80, 24, 128);
+    check_rdovae("rdovae_small", 32 | 64, 704, 40, 32, 64);
   }
   if (fails) {
     fprintf(stderr, "model_host_check: %d checks failed\n", fails);
     return 1;
   }
   printf("model_host_check ok (%d plans decoded, %d split, %d with the wide split form; %d declined by the planner; "
-         "%d PLC predictors decoded)\n",
-         plans, split_plans, wide_plans, declined, plc_decoded);
+         "%d PLC predictors and %d RDO-VAEs decoded)\n",
+         plans, split_plans, wide_plans, declined, plc_decoded, rdovae_decoded);
   return 0;
 }
