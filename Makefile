@@ -3,8 +3,9 @@
 #   make            -> lpcnet_amd/liblpcnet_mi355x.so + oracle/ libraries
 #   make lib        -> the product library only
 #   make check      -> builds and runs tools/model_host_check,
-#                      tools/pool_combiner_check, tools/conceal_plan_check
-#                      and tools/feat_host_check (CPU only)
+#                      tools/pool_combiner_check, tools/conceal_plan_check,
+#                      tools/device_mem_check and tools/feat_host_check
+#                      (CPU only)
 #
 # Every translation unit is compiled with -ffp-contract=off: the engine is
 # bit-exact with the reference x86 build only without FMA contraction.
@@ -15,10 +16,10 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/gru_tile.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h $(CSRC)/conceal_plan.h
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/gru_tile.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/device_mem.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h $(CSRC)/conceal_plan.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
-OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/synth_steps.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/rdovae_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/burg_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o $(BUILD)/conceal_kernel.o $(BUILD)/conceal_calls.o $(BUILD)/conceal_plan.o
+OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/device_mem.o $(BUILD)/synth_steps.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/rdovae_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/burg_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o $(BUILD)/conceal_kernel.o $(BUILD)/conceal_calls.o $(BUILD)/conceal_plan.o
 
 SYNTH := tools/lpcnet_synth
 DROPIN := tools/dropin_bench
@@ -44,7 +45,8 @@ $(BUILD):
 	mkdir -p $(BUILD)
 
 # The objects hipcc compiles, all with one command line: the kernels (.hip),
-# the batch (engine.cpp), its synthesis and decode calls and their launches
+# the batch (engine.cpp), the HIP backend of its memory owners
+# (device_mem.cpp), its synthesis and decode calls and their launches
 # (synth_steps.cpp), the drop-in single-stream API over them (dropin.cpp), the
 # PLC, feature, Burg, encoder and LPC calls beside synthesis (side_calls.cpp),
 # the concealment machine (conceal_calls.cpp) and the host-only GRU_A planner,
@@ -113,6 +115,14 @@ PLANCHECK := tools/conceal_plan_check
 $(PLANCHECK): tools/conceal_plan_check.cpp $(BUILD)/conceal_plan.o $(CSRC)/conceal_plan.h
 	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $< $(BUILD)/conceal_plan.o
 
+# stand-alone CPU check of the memory owners, the table uploads and the state
+# rows over a fake backend (tools/device_mem_check.cpp gives the sanitizer
+# recipe)
+MEMCHECK := tools/device_mem_check
+
+$(MEMCHECK): tools/device_mem_check.cpp $(CSRC)/device_mem.h
+	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) -o $@ $<
+
 # stand-alone check of what the side calls answer without a device, plain C
 # against the public header and the in-tree library
 # (tools/feat_host_check.c gives the sanitizer recipe)
@@ -121,19 +131,20 @@ FEATCHECK := tools/feat_host_check
 $(FEATCHECK): tools/feat_host_check.c include/lpcnet_mi355x.h $(LIB)
 	$(CC) -std=c99 -O2 -Wall -Wextra -Werror -Iinclude -o $@ $< -Llpcnet_amd -llpcnet_mi355x -Wl,-rpath,'$$ORIGIN/../lpcnet_amd'
 
-hostcheck: $(HOSTCHECK) $(POOLCHECK) $(PLANCHECK) $(FEATCHECK)
+hostcheck: $(HOSTCHECK) $(POOLCHECK) $(PLANCHECK) $(MEMCHECK) $(FEATCHECK)
 
 check: hostcheck
 	$(HOSTCHECK)
 	$(POOLCHECK)
 	$(PLANCHECK)
+	$(MEMCHECK)
 	$(FEATCHECK)
 
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK) $(PLANCHECK) $(FEATCHECK)
+	rm -rf $(BUILD) $(LIB) $(SYNTH) $(DROPIN) $(HOSTCHECK) $(POOLCHECK) $(PLANCHECK) $(MEMCHECK) $(FEATCHECK)
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib synth dropin hostcheck oracle clean check

@@ -1,12 +1,14 @@
 /*
  * batch.h -- what engine.cpp (the batch), synth_steps.cpp (its synthesis and
  * decode calls), dropin.cpp (the drop-in handles over them), side_calls.cpp
- * (the PLC, feature and LPC calls beside synthesis) and conceal_calls.cpp (the
- * concealment machine over all of them) share: struct LPCNetBatch, the
- * stream-state helpers, the timed regions, the partial-batch steps a StatePool
- * runs on its work batch and the machine on its work states, and what a
- * batch's load, reset and destruction call of side_calls.cpp and
- * conceal_calls.cpp.  Internal to those five files.
+ * (the PLC, feature, Burg, encoder, RDO-VAE and LPC calls beside synthesis)
+ * and conceal_calls.cpp (the concealment machine over all of them) share:
+ * struct LPCNetBatch and the buffer groups of the side calls, all of whose
+ * device memory, streams and events are held by device_mem.h's owners (so
+ * `delete b` releases them); the stream-state helpers, the timed regions, the
+ * partial-batch steps a StatePool runs on its work batch and the machine on
+ * its work states, and what a batch's load and reset call of side_calls.cpp
+ * and conceal_calls.cpp.  Internal to those five files.
  */
 #ifndef LPCNET_BATCH_H
 #define LPCNET_BATCH_H
@@ -21,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.h"
 #include "lpcnet_engine.h"
 #include "lpcnet_mi355x.h"
 #include "model_host.h"
@@ -38,20 +41,30 @@ using namespace lpcnet_mi355x;
     }                                                                                      \
   } while (0)
 
-/* lpcnet_batch_kernel_ms's `which`: 0..6, then 8 and 9 for the RDO-VAE.  7 is
- * no region and stays refused: callers probe it as the first invalid value. */
-constexpr int TIMED_REGIONS = 10;
-constexpr int TIMED_NONE = 7;
-constexpr int TIMED_RDOVAE_ENC = 8, TIMED_RDOVAE_DEC = 9;
+/* The timed regions: lpcnet_batch_kernel_ms's `which`.  7 is no region and
+ * stays refused: callers probe it as the first invalid value. */
+enum TimedRegion {
+  TIMED_SAMPLE = 0,     /* sample kernel */
+  TIMED_FRAME = 1,      /* frame kernel */
+  TIMED_PLC = 2,        /* PLC predictor */
+  TIMED_FEAT = 3,       /* feature extractor */
+  TIMED_ENC = 4,        /* encoder */
+  TIMED_ENC_KERNEL = 5, /* the part of the encoder that is enc_kernel.hip */
+  TIMED_BURG = 6,       /* Burg analysis (its three launches) */
+  TIMED_NONE = 7,
+  TIMED_RDOVAE_ENC = 8, /* RDO-VAE encoder */
+  TIMED_RDOVAE_DEC = 9, /* RDO-VAE decoder */
+  TIMED_REGIONS = 10
+};
 
 /* The device buffers of the calls beside synthesis (side_calls.cpp), one
- * value-initialised group per family: freeing a group is hipFree of what it
- * owns and `= {}`.
+ * value-initialised group per family.  A carved group owns its buffer (base)
+ * and keeps the planned pointers as plain members: freeing it is `= {}`.
  * PLC prediction network (plc_kernel.hip): each stream's plc_gru1_state |
  * plc_gru2_state outside StreamState (the synthesis snapshots keep their
- * size) and the host-I/O staging; they and the tables are LPCNetBatch's
- * plc_bufs, buffers of their own (a re-plan of the synthesis tables keeps
- * them). */
+ * size) and the host-I/O staging; they and the tables are buffers of their
+ * own, owned by LPCNetBatch's plc_bufs (a re-plan of the synthesis tables
+ * keeps them). */
 struct PlcBufs {
   float *state = nullptr;
   float *in = nullptr, *out = nullptr; /* [B][PLC_IN], [B][NF] */
@@ -62,7 +75,7 @@ struct PlcBufs {
  * host-I/O staging, one buffer (base) allocated by the first call that
  * extracts features (feat_ensure) */
 struct FeatBufs {
-  void *base = nullptr;
+  DevPtr<char> base;
   FeatState *state = nullptr;
   FeatTables *tab = nullptr;
   float *pcm = nullptr; /* [B][FRAME] float or short */
@@ -73,7 +86,7 @@ struct FeatBufs {
  * scratch of one call in one buffer, allocated by the first call that runs
  * it (burg_ensure); it shares the extractor's tables and host-I/O staging */
 struct BurgBufs {
-  void *base = nullptr;
+  DevPtr<char> base;
   BurgTables *tab = nullptr;
   double *c = nullptr; /* [BURG_NC][2 B] */
   float *x = nullptr;  /* [2 NLPC][2 B] */
@@ -84,7 +97,7 @@ struct BurgBufs {
  * (state, beside the extractor's; not the decoder's), the main_pitch table,
  * the scratch of one packet and the host-I/O staging */
 struct EncBufs {
-  void *base = nullptr;
+  DevPtr<char> base;
   float *vq = nullptr; /* [B][NBANDS] */
   EncTables *tab = nullptr;
   float *xc = nullptr, *fw = nullptr, *feat = nullptr, *lpc = nullptr;
@@ -102,45 +115,12 @@ struct EncBufs {
  * decode_all's scratch state, the concatenation scratch and the host-I/O
  * staging */
 struct RdovaeBufs {
-  void *base = nullptr;
+  DevPtr<char> base;
   float *enc_state = nullptr, *enc_mem = nullptr; /* [B][nt], [B][(ksize - 1) T] */
   float *dec_state = nullptr, *dec_scratch = nullptr; /* [B][nt] */
   float *cat = nullptr;                           /* [tiles][T max][PLC_TILE] */
   float *in = nullptr, *lat = nullptr, *st = nullptr, *out = nullptr; /* staging */
-  size_t lat_cap = 0, out_cap = 0;                /* floats the staging of latents / output holds */
   unsigned char *act = nullptr;
-};
-
-/* One device allocation carved into 256-byte-aligned parts: add(p, n) plans n
- * elements behind the pointer p; alloc() allocates the whole, sets every
- * planned pointer and returns the base (null, the pointers untouched, when the
- * device refuses). */
-class Carver {
-  struct Part {
-    void *ptr; /* the T * to set */
-    size_t off;
-  };
-  std::vector<Part> parts;
-  size_t bytes = 0;
-
- public:
-  template <class T>
-  void add(T *&p, size_t n)
-  {
-    parts.push_back({&p, bytes});
-    bytes += (n * sizeof(T) + 255) & ~(size_t)255;
-  }
-  size_t size() const { return bytes; }
-  void *alloc()
-  {
-    char *base = nullptr;
-    if (hipMalloc(&base, bytes) != hipSuccess) return nullptr;
-    for (const Part &q : parts) {
-      char *p = base + q.off;
-      memcpy(q.ptr, &p, sizeof(p));
-    }
-    return base;
-  }
 };
 
 struct ConcealMachine; /* conceal_calls.cpp */
@@ -149,7 +129,15 @@ struct ConcealMachine; /* conceal_calls.cpp */
 struct LPCNetBatch {
   int device = 0;
   int B = 0;
-  hipStream_t stream = nullptr;
+  /* Declared before every buffer, the streams before the events: members go
+   * in reverse order, so `delete b` frees the buffers, then destroys the
+   * events, then the streams.  fstream, ev_start, ev_frame and ev_samp are the
+   * overlapped multi-frame path's (below), ev_tick the end of a host-I/O tick
+   * (spin-polled), tev the timing events handed out since the last reset
+   * (taken) and those waiting for reuse (idle). */
+  DevStream stream, fstream;
+  DevEvent ev_frame[2], ev_samp[2], ev_start, ev_tick;
+  EventPool tev;
   /* model */
   bool have_model = false;
   int variant = 0;
@@ -174,69 +162,70 @@ struct LPCNetBatch {
   std::unique_ptr<HostModel> host;
   int image_bytes = 0;
   LPCNetModelInfo info{};
-  std::vector<void *> model_bufs;
+  DeviceTables model_bufs;
   FrameArgs fa{};
   SampleArgs sa{};
   /* streams */
-  StreamState *d_state = nullptr;
-  float *d_feat = nullptr;
-  short *d_pcm = nullptr;
-  float *d_lpc = nullptr;          /* [LPC_CHUNK][B][NLPC] lpc_from_cepstrum of queued frames */
-  LpcTables *d_lpc_tab = nullptr;
+  DevPtr<StreamState> d_state;
+  DevPtr<float> d_feat;
+  DevPtr<short> d_pcm;
+  DevPtr<float> d_lpc;             /* [LPC_CHUNK][B][NLPC] lpc_from_cepstrum of queued frames */
+  DevPtr<LpcTables> d_lpc_tab;
   /* overlapped multi-frame path (few streams, free CUs): frame kernel f+1 on
    * fstream beside sample kernel f on stream, outputs double-buffered in
    * d_cond[f & 1] */
-  hipStream_t fstream = nullptr;
-  FrameCond *d_cond[2] = {nullptr, nullptr};
-  hipEvent_t ev_frame[2] = {nullptr, nullptr}, ev_samp[2] = {nullptr, nullptr}, ev_start = nullptr;
+  DevPtr<FrameCond> d_cond[2];
   bool ev_samp_used[2] = {false, false};
   hipEvent_t ev_samp_cur[2] = {nullptr, nullptr}; /* the event slot c's reuse waits on */
   /* chunked multi-frame path (batches above OVERLAP_MAX_STREAMS): the frame
    * network of up to LPC_CHUNK frames in one chunk_kernel launch, outputs of
    * frame f in d_chunk[f][B] */
-  FrameCond *d_chunk = nullptr;
+  DevPtr<FrameCond> d_chunk;
   bool chunking = true;
   /* per-frame host-I/O path of large batches (synth_first): one frame's
    * chunk_kernel outputs [B], and pinned staging of the caller's features and
-   * PCM (so both copies are asynchronous, behind one synchronisation) */
+   * PCM (so both copies are asynchronous, behind one synchronisation).
+   * The features live in one of two owners, of which h_io_feat / d_io_feat
+   * are the views the hot path reads. */
+  DevPtr<float> io_feat_dev;     /* host-visible device memory (fine-grained VRAM, large BAR), or */
+  PinnedPtr<float> io_feat_host; /* mapped pinned host memory */
   float *h_io_feat = nullptr;
-  short *h_io_pcm = nullptr;
+  float *d_io_feat = nullptr; /* h_io_feat's device address */
+  bool io_feat_vram = false;  /* h_io_feat is io_feat_dev's */
+  PinnedPtr<short> h_io_pcm;
   short *d_io_pcm = nullptr; /* h_io_pcm's device address (mapped) */
-  float *d_io_feat = nullptr; /* h_io_feat's device address (mapped) */
-  bool io_feat_vram = false;  /* h_io_feat is host-visible device memory (fine-grained VRAM, large BAR) */
-  float *h_stg_feat = nullptr; /* pinned staging of the caller's own buffers */
-  short *h_stg_pcm = nullptr;
-  hipEvent_t ev_tick = nullptr; /* end of a host-I/O tick (spin-polled) */
+  PinnedPtr<float> h_stg_feat; /* pinned staging of the caller's own buffers */
+  PinnedPtr<short> h_stg_pcm;
   /* trace */
   bool trace = false;
-  float *d_trace_logits = nullptr;
-  int *d_trace_exc = nullptr;
+  DevPtr<float> d_trace_logits; /* both or neither (ensure_trace) */
+  DevPtr<int> d_trace_exc;
   int trace_N = 0;
   /* device -> host status word (pinned, mapped): a kernel that aborts sets
    * STATUS_* bits; every synchronising entry point checks and clears it */
-  int *h_status = nullptr;
-  int *d_status = nullptr;
-  int *d_ck_sync = nullptr; /* [ceil(B / 16)] arrival counters of the sliced one-frame chunk kernel */
+  PinnedPtr<int> h_status;
+  int *d_status = nullptr; /* h_status's device address */
+  DevPtr<int> d_ck_sync; /* [ceil(B / 16)] arrival counters of the sliced one-frame chunk kernel */
   int spin_limit = FLAG_SPIN_LIMIT_DEFAULT;
   /* 1.6 kb/s decoder (decode_kernel.hip): the model's ceps codebooks (optional
    * blob records), packets and decoded features of up to DEC_MAX_PACKETS
    * packets per stream, the host-I/O path's 4-frame PCM */
   DecodeArgs da{};
   bool has_codebooks = false;
-  unsigned char *d_packets = nullptr;
-  float *d_dfeat = nullptr;
-  short *d_dpcm = nullptr;
+  DevPtr<unsigned char> d_packets;
+  DevPtr<float> d_dfeat;
+  DevPtr<short> d_dpcm;
   /* PLC prediction network: optional blob records */
   bool plc_ok = false;
   std::string plc_why = "no model loaded"; /* why the PLC calls refuse this batch */
   PlcArgs pa{};
-  std::vector<void *> plc_bufs;
+  DeviceTables plc_bufs; /* the tables, then the state and staging plc points into */
   /* DRED RDO-VAE: optional blob records, each side on its own */
   bool rdo_ok[2] = {false, false}; /* encoder, decoder */
   std::string rdo_why[2] = {"no model loaded", "no model loaded"};
   RdovaeNet rdo_net[2] = {};
   int rdo_dims[RDOVAE_DIMS] = {};
-  std::vector<void *> rdovae_bufs;
+  DeviceTables rdovae_bufs;
   RdovaeBufs rdo{};
   /* the buffers of the calls beside synthesis */
   PlcBufs plc{};
@@ -246,15 +235,11 @@ struct LPCNetBatch {
   /* the concealment machine (lpcnet_batch_conceal_open), null without one */
   ConcealMachine *conceal = nullptr;
   /* diagnostics */
-  unsigned long long *d_stamps = nullptr;
+  DevPtr<unsigned long long> d_stamps;
   /* timing */
   int timing = 0;        /* 0 off, 1 sample kernel, 2 sample + frame kernel */
-  std::vector<hipEvent_t> ev_taken; /* events handed out since the last reset */
-  /* sample kernel, frame kernel, PLC predictor, feature extractor, encoder, the encoder's enc_kernel part, Burg analysis,
-   * none, RDO-VAE encoder, RDO-VAE decoder */
-  std::vector<hipEvent_t> ev_pairs[TIMED_REGIONS];
-  std::vector<int> ev_frames[TIMED_REGIONS];    /* frames covered by each pair */
-  std::vector<hipEvent_t> ev_free;
+  std::vector<hipEvent_t> ev_pairs[TIMED_REGIONS]; /* per TimedRegion: (start, end) events of tev */
+  std::vector<int> ev_frames[TIMED_REGIONS];       /* frames covered by each pair */
   /* lower bound of every stream's frame_count (lpcnet.c:119) before the next
    * frame: the multi-frame sample launches start where no stream can still
    * be inside its first `delay` (FEATURES_DELAY) frames */
@@ -279,13 +264,13 @@ bool gru_state_plausible(const float *v, size_t n);
 
 /* Timed regions (lpcnet_batch_kernel_ms; engine.cpp).  mark: with `on`, take
  * an event and record it on `s` (e = nullptr otherwise).  timed: the pair
- * (e0, e1) covers `frames` frames of region `which` (0 sample kernel, 1 frame
- * kernel, 2 PLC predictor, 3 feature extractor, 4 encoder, 5 the part of 4
- * that is enc_kernel.hip, 6 Burg analysis); a null event: no pair. */
+ * (e0, e1) covers `frames` frames of region `which` (a TimedRegion); a null
+ * event: no pair. */
 int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e);
 void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames);
 /* engine.cpp.  ensure_trace: before the sample launches of a call of N samples
- * per frame, the batch's trace buffers (allocated here) in b->sa, or none.
+ * per frame, the batch's trace buffers (allocated here, both or neither) in
+ * b->sa, or none.
  * check_status: after a sync of b->stream, report (set_err, -1) and clear a
  * device-side abort. */
 int ensure_trace(LPCNetBatch *b, int N);
@@ -345,7 +330,7 @@ void rdovae_free(LPCNetBatch *b);
 enum { SIDE_PLC = 1, SIDE_FEAT = 2 };
 int side_reset(LPCNetBatch *b, int stream, int parts);
 /* the single launches of the side calls on b->stream, each a timed region
- * (2 predictor, 3 extractor, 6 Burg analysis), and what they need ready:
+ * (TIMED_PLC, TIMED_FEAT, TIMED_BURG), and what they need ready:
  * plc_ready (a model with usable PLC records; set_err otherwise), burg_ensure
  * (the extractor's and the Burg tables and scratch) */
 int plc_ready(const LPCNetBatch *b);

@@ -45,7 +45,7 @@ static_assert(CONCEAL_FEC_ROWS == CONCEAL_MAX_FEC && CONCEAL_DEFER == CONCEAL_DE
 struct ConcealMachine {
   int options = 0;
   ConcealData d{};
-  void *base = nullptr;          /* the carved device buffer */
+  DevPtr<char> base;             /* the carved device buffer */
   StreamState *work = nullptr;   /* [B] the states a synthesis step runs on */
   short *io = nullptr;           /* [B][FRAME] the host form's PCM */
   std::vector<ConcealCtrl> ctrl; /* [B] */
@@ -53,14 +53,14 @@ struct ConcealMachine {
   /* a tick's index lists and masks: built in a pinned slot, one copy into
    * d_lists.  A slot is rewritten once the copy that read it has run. */
   struct Slot {
-    char *h = nullptr;
-    hipEvent_t ev = nullptr;
+    PinnedPtr<char> h;
+    DevEvent ev;
     bool used = false;
   };
   static constexpr int SLOTS = 4;
   Slot ring[SLOTS];
   int next = 0;
-  char *d_lists = nullptr;
+  DevPtr<char> d_lists;
   size_t cap = 0;
   /* what d_lists holds: a tick with the same lists (the steady state: every
    * stream received its packet again) copies nothing */
@@ -160,29 +160,28 @@ int plan_batch_tick(const ConcealMachine &M, int B, const unsigned char *lost, c
 int upload_lists(LPCNetBatch *b, ConcealMachine &M, const TickPlan &T, const int *&d_idx, const unsigned char *&d_mask)
 {
   const size_t idx_bytes = (T.idx.size() * sizeof(int) + 255) & ~(size_t)255, bytes = idx_bytes + T.mask.size();
-  d_idx = (const int *)M.d_lists;
-  d_mask = (const unsigned char *)M.d_lists + idx_bytes;
+  d_idx = (const int *)(char *)M.d_lists;
+  d_mask = (const unsigned char *)(char *)M.d_lists + idx_bytes;
   if (M.up_valid && T.idx == M.up_idx && T.mask == M.up_mask) return 0;
   M.up_valid = false;
   if (bytes > M.cap) {
     /* grow: nothing queued may still read the old lists */
     HIPCHK(hipStreamSynchronize(b->stream));
     const size_t cap = std::max(bytes * 2, (size_t)4096);
-    (void)hipFree(M.d_lists);
-    M.d_lists = nullptr;
+    M.d_lists.reset();
     M.cap = 0;
     for (ConcealMachine::Slot &s : M.ring) {
-      (void)hipHostFree(s.h);
-      s.h = nullptr;
+      s.h.reset();
       s.used = false;
     }
-    HIPCHK(hipMalloc(&M.d_lists, cap));
-    for (ConcealMachine::Slot &s : M.ring) HIPCHK(hipHostMalloc(&s.h, cap, hipHostMallocDefault));
+    if (M.d_lists.alloc(cap)) return -1;
+    for (ConcealMachine::Slot &s : M.ring)
+      if (s.h.alloc(cap, false)) return -1;
     M.cap = cap;
   }
   ConcealMachine::Slot &s = M.ring[M.next];
   M.next = (M.next + 1) % ConcealMachine::SLOTS;
-  if (!s.ev) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  if (!s.ev && s.ev.create(false)) return -1;
   if (s.used) HIPCHK(hipEventSynchronize(s.ev)); /* the copy of four ticks ago */
   memcpy(s.h, T.idx.data(), T.idx.size() * sizeof(int));
   if (!T.mask.empty()) memcpy(s.h + idx_bytes, T.mask.data(), T.mask.size());
@@ -192,8 +191,8 @@ int upload_lists(LPCNetBatch *b, ConcealMachine &M, const TickPlan &T, const int
   M.up_idx = T.idx;
   M.up_mask = T.mask;
   M.up_valid = true;
-  d_idx = (const int *)M.d_lists;
-  d_mask = (const unsigned char *)M.d_lists + idx_bytes;
+  d_idx = (const int *)(char *)M.d_lists;
+  d_mask = (const unsigned char *)(char *)M.d_lists + idx_bytes;
   return 0;
 }
 
@@ -311,12 +310,6 @@ void conceal_free(LPCNetBatch *b)
   ConcealMachine *M = b->conceal;
   if (!M) return;
   (void)hipStreamSynchronize(b->stream);
-  (void)hipFree(M->base);
-  (void)hipFree(M->d_lists);
-  for (ConcealMachine::Slot &s : M->ring) {
-    (void)hipHostFree(s.h);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-  }
   delete M;
   b->conceal = nullptr;
 }
@@ -330,14 +323,14 @@ int conceal_reset_streams(LPCNetBatch *b, int stream)
   if (!M) return 0;
   const ConcealData &d = M->d;
   const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)b->B : 1;
-  const auto zero = [&](void *p, size_t per_stream) { return hipMemsetAsync((char *)p + first * per_stream, 0, n * per_stream, b->stream); };
-  HIPCHK(zero(d.features, NF * 4));
-  HIPCHK(zero(d.pcm, (size_t)(d.buf + FRAME) * 2));
-  HIPCHK(zero(d.dc, 16));
-  HIPCHK(zero(d.copy, (size_t)(d.delay + 1) * d.nt * 4));
-  HIPCHK(zero(d.fec, (size_t)CONCEAL_FEC_ROWS * NF * 4));
-  HIPCHK(zero(d.defer, (size_t)CONCEAL_DEFER * NF * 4));
-  HIPCHK(zero(d.delta, 4));
+  const std::vector<StateRows> rows = {{d.features, NF * 4},
+                                       {d.pcm, (size_t)(d.buf + FRAME) * 2},
+                                       {d.dc, 16},
+                                       {d.copy, (size_t)(d.delay + 1) * d.nt * 4},
+                                       {d.fec, (size_t)CONCEAL_FEC_ROWS * NF * 4},
+                                       {d.defer, (size_t)CONCEAL_DEFER * NF * 4},
+                                       {d.delta, 4}};
+  if (rows_zero(rows, stream, b->B, b->stream)) return -1;
   for (size_t s = first; s < first + n; s++) M->ctrl[s] = conceal_ctrl_reset(d.delay);
   return 0;
 }
@@ -388,7 +381,6 @@ LPCNET_EXPORT int lpcnet_batch_conceal_open(LPCNetBatch *b, int options)
   if (!M->base || hipMemsetAsync(M->base, 0, c.size(), b->stream) != hipSuccess ||
       hipMemcpyAsync(w, win, sizeof(win), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
       hipStreamSynchronize(b->stream) != hipSuccess) { /* win leaves scope */
-    (void)hipFree(M->base);
     set_err("conceal: device allocation failed");
     return -1;
   }

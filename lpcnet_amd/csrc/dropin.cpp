@@ -55,13 +55,13 @@ struct StatePool {
   /* the work batch (its HIP stream) and its staging, driven by the combiner */
   struct Lane {
     LPCNetBatch *work = nullptr; /* work->B >= the largest coalesced call */
-    int *d_map = nullptr;        /* [map_cap] work-batch stream -> slot */
+    DevPtr<int> d_map;           /* [map_cap] work-batch stream -> slot */
     int map_cap = 0;
     /* pinned host staging of a launch ([map_cap] entries each), so the
      * copies are truly asynchronous: slot map, features, PCM */
-    int *h_map = nullptr;
-    float *h_feat = nullptr;
-    short *h_pcm = nullptr;
+    PinnedPtr<int> h_map;
+    PinnedPtr<float> h_feat;
+    PinnedPtr<short> h_pcm;
   };
   uint64_t key = 0;
   int device = 0;
@@ -69,7 +69,7 @@ struct StatePool {
   std::vector<unsigned char> blob;
   bool has_codebooks = false;
   Lane lane;
-  StreamState *d_slots = nullptr;
+  DevPtr<StreamState> d_slots;
   int cap = 0;
   std::vector<int> free_slots;
   int refs = 0; /* handles bound + transient acquisitions; changed under g_pools_mu only */
@@ -168,14 +168,9 @@ static void pool_release(StatePool *p, int slot)
     if (--p->refs > 0) return;
     g_pools.erase({p->key, p->place});
   }
-  /* unreachable now: no handle holds it and the map no longer lists it */
-  if (hipSetDevice(p->device) == hipSuccess) {
-    (void)hipFree(p->d_slots);
-    (void)hipFree(p->lane.d_map);
-    (void)hipHostFree(p->lane.h_map);
-    (void)hipHostFree(p->lane.h_feat);
-    (void)hipHostFree(p->lane.h_pcm);
-  }
+  /* unreachable now: no handle holds it and the map no longer lists it;
+   * its owners free the slots and the lane's staging on the pool's device */
+  (void)hipSetDevice(p->device);
   if (p->lane.work) lpcnet_batch_destroy(p->lane.work);
   delete p;
 }
@@ -188,15 +183,13 @@ static int pool_alloc_slot(StatePool *p, const StreamState *init)
   if (hipSetDevice(p->device) != hipSuccess) { set_err("hipSetDevice failed"); return -1; }
   if (p->free_slots.empty()) {
     const int ncap = std::max(4, 2 * p->cap);
-    StreamState *d = nullptr;
-    if (hipMalloc(&d, sizeof(StreamState) * (size_t)ncap) != hipSuccess) { set_err("device allocation failed"); return -1; }
+    DevPtr<StreamState> d;
+    if (d.alloc((size_t)ncap)) { set_err("device allocation failed"); return -1; }
     if (p->cap && hipMemcpy(d, p->d_slots, sizeof(StreamState) * (size_t)p->cap, hipMemcpyDeviceToDevice) != hipSuccess) {
-      (void)hipFree(d);
       set_err("device copy failed");
       return -1;
     }
-    (void)hipFree(p->d_slots);
-    p->d_slots = d;
+    p->d_slots.swap(d); /* the previous slots go with d */
     for (int k = ncap - 1; k >= p->cap; k--) p->free_slots.push_back(k);
     p->cap = ncap;
   }
@@ -247,19 +240,13 @@ static int pool_run(StatePool *p, StatePool::Lane &L, const std::vector<Req *> &
   LPCNetBatch *w = L.work;
   if (w->set_device()) return -1;
   if (L.map_cap < n) {
-    (void)hipFree(L.d_map);
-    (void)hipHostFree(L.h_map);
-    (void)hipHostFree(L.h_feat);
-    (void)hipHostFree(L.h_pcm);
-    L.d_map = nullptr;
-    L.h_map = nullptr;
-    L.h_feat = nullptr;
-    L.h_pcm = nullptr;
+    L.d_map.reset();
+    L.h_map.reset();
+    L.h_feat.reset();
+    L.h_pcm.reset();
     L.map_cap = 0;
-    HIPCHK(hipMalloc(&L.d_map, sizeof(int) * (size_t)w->B));
-    HIPCHK(hipHostMalloc(&L.h_map, sizeof(int) * (size_t)w->B, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&L.h_feat, sizeof(float) * NF * (size_t)w->B, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&L.h_pcm, sizeof(short) * 4 * FRAME * (size_t)w->B, hipHostMallocDefault));
+    const size_t nw = (size_t)w->B;
+    if (L.d_map.alloc(nw) || L.h_map.alloc(nw, false) || L.h_feat.alloc(NF * nw, false) || L.h_pcm.alloc(4 * FRAME * nw, false)) return -1;
     L.map_cap = w->B;
   }
   float *feat = L.h_feat;

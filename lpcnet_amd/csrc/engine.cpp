@@ -6,10 +6,14 @@
  * under them are synth_steps.cpp.  The drop-in single-stream API of
  * include/lpcnet.h is dropin.cpp, over the partial-batch steps declared in
  * batch.h.  The calls beside synthesis -- the PLC predictor, the feature
- * extractor and lpcnet_mi355x_device_lpc -- are side_calls.cpp, their
- * host-built tables side_tables.cpp (host-only); this file loads and frees
- * the PLC tables with the model (plc_load, plc_free) and lends them its timed
- * regions (batch.h).
+ * extractor, the Burg analysis, the encoder, the RDO-VAE and
+ * lpcnet_mi355x_device_lpc -- are side_calls.cpp, which also loads and frees
+ * their tables (plc_load, rdovae_load, called from a model load here); their
+ * host-built tables are side_tables.cpp (host-only).  This file lends them
+ * its timed regions (batch.h).  Every buffer, stream and event of a batch is
+ * held by an owner of device_mem.h, whose HIP backend is device_mem.cpp: no
+ * file but that one allocates or frees (the public allocator
+ * lpcnet_batch_device_alloc / _free below aside).
  *
  * Responsibilities
  *  - upload of a parsed, validated and re-tiled weight blob (model_host.cpp:
@@ -111,22 +115,9 @@ namespace {
 
 void free_model(LPCNetBatch *b)
 {
-  for (void *p : b->model_bufs) (void)hipFree(p);
   b->model_bufs.clear();
   b->have_model = false;
   b->ck_warm = L2Warm{};
-}
-
-hipEvent_t get_event(LPCNetBatch *b)
-{
-  if (!b->ev_free.empty()) {
-    hipEvent_t e = b->ev_free.back();
-    b->ev_free.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
-  return e;
 }
 
 /* what the kernel choice (kernel_choice.cpp) takes from a host model, and
@@ -191,22 +182,11 @@ ModelBuildOpts build_opts(int streams, bool wide)
 
 /* One device buffer per entry of the model's upload list, its address in
  * the entry's member of `args`.  On any failure frees what it allocated. */
-int upload_model(const HostModel &host, ModelArgs &args, std::vector<void *> &bufs)
+int upload_model(const HostModel &host, ModelArgs &args, DeviceTables &bufs)
 {
-  const std::vector<ModelUpload> up = model_uploads(host, args);
-  for (const ModelUpload &u : up) {
-    if (!u.present) continue;
-    void *p = nullptr;
-    bool ok = hipMalloc(&p, u.bytes ? u.bytes : 16) == hipSuccess;
-    if (ok) bufs.push_back(p);
-    ok = ok && (!u.bytes || hipMemcpy(p, u.src, u.bytes, hipMemcpyHostToDevice) == hipSuccess);
-    if (!ok) {
-      for (void *q : bufs) (void)hipFree(q);
-      bufs.clear();
-      set_err("device upload failed");
-      return -1;
-    }
-    memcpy(u.dst, &p, sizeof(p));
+  if (bufs.upload(model_uploads(host, args))) {
+    set_err("device upload failed");
+    return -1;
   }
   return 0;
 }
@@ -229,14 +209,13 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, HostModel &ho
   if (b->set_device()) { set_err("hipSetDevice failed"); return -1; }
   if (!replan) free_model(b);
   ModelArgs args;
-  std::vector<void *> bufs;
+  DeviceTables bufs;
   if (upload_model(host, args, bufs)) return -1;
   if (!host.bounds_note.empty()) fputs(host.bounds_note.c_str(), stderr);
   /* Nothing in *b (a fresh load's freed buffers aside) has changed up to
    * here, and nothing below can fail: every check passed and the last upload
    * succeeded. */
-  for (void *p : b->model_bufs) (void)hipFree(p); /* a replan's previous tables */
-  b->model_bufs = bufs;
+  b->model_bufs = std::move(bufs); /* frees a replan's previous tables */
   b->sa = args.sa;
   b->fa = args.fa;
   b->da = args.da;
@@ -273,8 +252,12 @@ int lpcnet_mi355x::ensure_trace(LPCNetBatch *b, int N)
     return 0;
   }
   if (!b->d_trace_logits) {
-    HIPCHK(hipMalloc(&b->d_trace_logits, (size_t)b->B * FRAME * 8 * 4));
-    HIPCHK(hipMalloc(&b->d_trace_exc, (size_t)b->B * FRAME * 4));
+    /* both or neither: a batch never holds one without the other */
+    DevPtr<float> logits;
+    DevPtr<int> exc;
+    if (logits.alloc((size_t)b->B * FRAME * 8) || exc.alloc((size_t)b->B * FRAME)) return -1;
+    b->d_trace_logits = std::move(logits);
+    b->d_trace_exc = std::move(exc);
   }
   b->sa.trace_logits = b->d_trace_logits;
   b->sa.trace_exc = b->d_trace_exc;
@@ -285,17 +268,15 @@ int lpcnet_mi355x::ensure_trace(LPCNetBatch *b, int N)
 /* ---- timed regions (lpcnet_batch_kernel_ms; batch.h) ---------------------- */
 /* mark: with `on`, take an event and record it on `s` (e = nullptr
  * otherwise: with timing off there are no events at all).  The event belongs
- * to ev_taken from the moment it is taken, so a failing call leaks nothing.
- * timed: the pair (e0, e1) covers `frames` frames of region `which` (0 sample
- * kernel, 1 frame kernel, 2 PLC predictor, 3 feature extractor, 4 and 5 the
- * encoder, 6 the Burg analysis, 8 and 9 the RDO-VAE encoder and decoder). */
+ * to tev.taken from the moment it is taken, so a failing call leaks nothing.
+ * timed: the pair (e0, e1) covers `frames` frames of region `which` (a
+ * TimedRegion, batch.h). */
 int lpcnet_mi355x::mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e)
 {
   e = nullptr;
   if (!on) return 0;
-  e = get_event(b);
+  e = b->tev.take();
   if (!e) { set_err("hipEventCreate failed"); return -1; }
-  b->ev_taken.push_back(e);
   HIPCHK(hipEventRecord(e, s));
   return 0;
 }
@@ -311,9 +292,10 @@ void lpcnet_mi355x::timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e
 /* After a sync of b->stream: report (and clear) a device-side abort. */
 int lpcnet_mi355x::check_status(LPCNetBatch *b)
 {
-  const int st = __atomic_load_n(b->h_status, __ATOMIC_ACQUIRE);
+  int *const word = b->h_status;
+  const int st = __atomic_load_n(word, __ATOMIC_ACQUIRE);
   if (st == 0) return 0;
-  __atomic_store_n(b->h_status, 0, __ATOMIC_RELEASE);
+  __atomic_store_n(word, 0, __ATOMIC_RELEASE);
   if (st & STATUS_FLAG_TIMEOUT)
     set_err("device abort: an LDS flag wait in the sample kernel exceeded its spin limit; the PCM of this call is invalid");
   else if (st & STATUS_SLICE_TIMEOUT)
@@ -440,17 +422,18 @@ LPCNET_EXPORT LPCNetBatch *lpcnet_batch_create(int nb_streams, int device)
   b->device = device;
   b->B = nb_streams;
   bool ok = b->set_device() == 0;
-  ok = ok && hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_state, sizeof(StreamState) * (size_t)nb_streams) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_feat, sizeof(float) * NF * (size_t)nb_streams) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_pcm, sizeof(short) * FRAME * (size_t)nb_streams) == hipSuccess;
-  ok = ok && hipHostMalloc(&b->h_status, 64, hipHostMallocMapped) == hipSuccess;
+  const size_t nB = (size_t)nb_streams;
+  ok = ok && b->stream.create() == 0;
+  ok = ok && b->d_state.alloc(nB) == 0;
+  ok = ok && b->d_feat.alloc(NF * nB) == 0;
+  ok = ok && b->d_pcm.alloc(FRAME * nB) == 0;
+  ok = ok && b->h_status.alloc(64 / sizeof(int), true) == 0;
   ok = ok && hipHostGetDevicePointer((void **)&b->d_status, b->h_status, 0) == hipSuccess;
   if (ok) *b->h_status = 0;
-  ok = ok && hipMalloc(&b->d_lpc, sizeof(float) * NLPC * (size_t)nb_streams * LPC_CHUNK) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_ck_sync, sizeof(int) * (size_t)((nb_streams + 15) / 16)) == hipSuccess;
-  ok = ok && hipMemset(b->d_ck_sync, 0, sizeof(int) * (size_t)((nb_streams + 15) / 16)) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_lpc_tab, sizeof(LpcTables)) == hipSuccess;
+  ok = ok && b->d_lpc.alloc(NLPC * nB * LPC_CHUNK) == 0;
+  ok = ok && b->d_ck_sync.alloc((nB + 15) / 16) == 0;
+  ok = ok && hipMemset(b->d_ck_sync, 0, sizeof(int) * ((nB + 15) / 16)) == hipSuccess;
+  ok = ok && b->d_lpc_tab.alloc(1) == 0;
   /* d_chunk (the chunked path's frame outputs, LPC_CHUNK x 4.9 KB per
    * stream) is allocated by the first call that takes that path */
   if (ok) {
@@ -459,12 +442,12 @@ LPCNET_EXPORT LPCNetBatch *lpcnet_batch_create(int nb_streams, int device)
     ok = hipMemcpy(b->d_lpc_tab, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
   }
   if (ok && nb_streams <= OVERLAP_MAX_STREAMS) {
-    ok = ok && hipStreamCreateWithFlags(&b->fstream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&b->ev_start, hipEventDisableTiming) == hipSuccess;
+    ok = ok && b->fstream.create() == 0;
+    ok = ok && b->ev_start.create(false) == 0;
     for (int i = 0; i < 2 && ok; i++) {
-      ok = ok && hipMalloc(&b->d_cond[i], sizeof(FrameCond) * (size_t)nb_streams) == hipSuccess;
-      ok = ok && hipEventCreateWithFlags(&b->ev_frame[i], hipEventDisableTiming) == hipSuccess;
-      ok = ok && hipEventCreateWithFlags(&b->ev_samp[i], hipEventDisableTiming) == hipSuccess;
+      ok = ok && b->d_cond[i].alloc(nB) == 0;
+      ok = ok && b->ev_frame[i].create(false) == 0;
+      ok = ok && b->ev_samp[i].create(false) == 0;
     }
   }
   if (!ok) {
@@ -484,40 +467,7 @@ LPCNET_EXPORT void lpcnet_batch_destroy(LPCNetBatch *b)
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->fstream) (void)hipStreamSynchronize(b->fstream);
   conceal_free(b);
-  free_model(b);
-  plc_free(b);
-  rdovae_free(b);
-  feat_free(b);
-  (void)hipFree(b->d_state);
-  (void)hipFree(b->d_ck_sync);
-  (void)hipFree(b->d_feat);
-  (void)hipFree(b->d_pcm);
-  (void)hipFree(b->d_trace_logits);
-  (void)hipFree(b->d_trace_exc);
-  (void)hipFree(b->d_stamps);
-  (void)hipFree(b->d_lpc);
-  (void)hipFree(b->d_lpc_tab);
-  (void)hipFree(b->d_chunk);
-  if (b->io_feat_vram) (void)hipFree(b->h_io_feat);
-  else (void)hipHostFree(b->h_io_feat);
-  (void)hipHostFree(b->h_io_pcm);
-  (void)hipHostFree(b->h_stg_feat);
-  (void)hipHostFree(b->h_stg_pcm);
-  if (b->ev_tick) (void)hipEventDestroy(b->ev_tick);
-  (void)hipFree(b->d_packets);
-  (void)hipFree(b->d_dfeat);
-  (void)hipFree(b->d_dpcm);
-  for (int i = 0; i < 2; i++) {
-    (void)hipFree(b->d_cond[i]);
-    if (b->ev_frame[i]) (void)hipEventDestroy(b->ev_frame[i]);
-    if (b->ev_samp[i]) (void)hipEventDestroy(b->ev_samp[i]);
-  }
-  if (b->h_status) (void)hipHostFree(b->h_status);
-  if (b->ev_start) (void)hipEventDestroy(b->ev_start);
-  if (b->fstream) (void)hipStreamDestroy(b->fstream);
-  for (hipEvent_t e : b->ev_taken) (void)hipEventDestroy(e);
-  for (hipEvent_t e : b->ev_free) (void)hipEventDestroy(e);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
+  /* the device is current: the owners free the buffers, then the events, then the streams */
   delete b;
 }
 
@@ -659,17 +609,14 @@ LPCNET_EXPORT int lpcnet_batch_state_size(void) { return (int)sizeof(StreamState
 LPCNET_EXPORT int lpcnet_batch_save_state(LPCNetBatch *b, int stream, void *buf)
 {
   if (!b || stream < 0 || stream >= b->B || !buf || b->set_device()) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, &b->d_state[stream], sizeof(StreamState), hipMemcpyDeviceToHost));
-  return 0;
+  return rows_save({{b->d_state, sizeof(StreamState)}}, stream, buf, b->stream);
 }
 
 LPCNET_EXPORT int lpcnet_batch_restore_state(LPCNetBatch *b, int stream, const void *buf)
 {
   if (!b || stream < 0 || stream >= b->B || !buf || b->set_device()) return -1;
   if (!snapshot_ok(buf)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(&b->d_state[stream], buf, sizeof(StreamState), hipMemcpyHostToDevice));
+  if (rows_restore({{b->d_state, sizeof(StreamState)}}, stream, buf, b->stream)) return -1;
   int fc;
   memcpy(&fc, (const unsigned char *)buf + offsetof(StreamState, frame_count), sizeof(fc));
   b->min_fc = std::min(b->min_fc, fc);
@@ -740,8 +687,7 @@ LPCNET_EXPORT void lpcnet_batch_reset_timers(LPCNetBatch *b, int enable)
   }
   /* stream is idle (and fstream with it): no slot reuse needs a wait */
   b->ev_samp_used[0] = b->ev_samp_used[1] = false;
-  for (hipEvent_t e : b->ev_taken) b->ev_free.push_back(e);
-  b->ev_taken.clear();
+  b->tev.recycle();
   b->timing = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
 }
 
@@ -778,13 +724,12 @@ LPCNET_EXPORT int lpcnet_batch_set_stamps(LPCNetBatch *b, int enable)
 {
   if (!b || b->set_device()) return -1;
   (void)hipStreamSynchronize(b->stream);
-  if (b->d_stamps) (void)hipFree(b->d_stamps);
-  b->d_stamps = nullptr;
+  b->d_stamps.reset();
   if (enable) {
     /* sample kernel [groups][STAMP_WAVES][16] (enough for any S), then the
      * frame kernel [B / FRAME_STREAMS][16] */
     size_t n = (size_t)b->B * STAMP_WAVES * 16 + (size_t)(frame_groups(b->B) + 1) * 16;
-    HIPCHK(hipMalloc(&b->d_stamps, n * 8));
+    if (b->d_stamps.alloc(n)) return -1;
     HIPCHK(hipMemset(b->d_stamps, 0, n * 8));
   }
   return 0;

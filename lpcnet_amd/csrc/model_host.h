@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.h"
 #include "lpcnet_engine.h"
 #include "lpcnet_mi355x.h"
 #include "mf_plan.h"
@@ -133,12 +134,7 @@ struct ModelArgs {
   SampleArgs sa;
   DecodeArgs da;
 };
-struct ModelUpload {
-  void *dst; /* address of a pointer member of ModelArgs */
-  const void *src;
-  size_t bytes;
-  bool present;
-};
+/* struct ModelUpload: device_mem.h, beside DeviceTables::upload */
 constexpr int MODEL_TABLES = 56;
 /* sets the scalar members of `a` and returns the MODEL_TABLES entries */
 std::vector<ModelUpload> model_uploads(const HostModel &h, ModelArgs &a);

@@ -6,9 +6,13 @@
  * _plc_update*), the 1.6 kb/s encoder (lpcnet_batch_encode*), the DRED
  * RDO-VAE (lpcnet_batch_rdovae_*) and the stand-alone
  * lpcnet_mi355x_device_lpc.
- * Their tables are built host-only in side_tables.cpp; the batch they run on
- * and its timed regions are engine.cpp's (batch.h).  Argument errors are
- * reported before any device call.
+ * Their tables are built host-only in side_tables.cpp and uploaded here
+ * with a model load (plc_load, rdovae_load); the lazily allocated buffers of
+ * each family are carved groups that own their memory (batch.h,
+ * device_mem.h), and every reset, save and restore of per-stream state is a
+ * list of StateRows.  The batch they run on and its timed regions are
+ * engine.cpp's (batch.h).  Argument errors are reported before any device
+ * call.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -32,6 +36,12 @@ int copy_back_active(LPCNetBatch *b, const void *d_rows, size_t row, void *out, 
   return 0;
 }
 
+/* the per-stream state of each family as rows (device_mem.h): the
+ * predictor's GRU states, the analysis state, the encoder's vq_mem */
+StateRows plc_rows_of(const LPCNetBatch *b) { return {b->plc.state, ((size_t)b->pa.n1 + b->pa.n2) * 4}; }
+StateRows feat_rows_of(const LPCNetBatch *b) { return {b->feat.state, sizeof(FeatState)}; }
+StateRows vq_rows_of(const LPCNetBatch *b) { return {b->enc.vq, NBANDS * 4}; }
+
 }  // namespace
 
 /* ---- PLC prediction network (plc_kernel.hip) ------------------------------ */
@@ -39,7 +49,6 @@ namespace lpcnet_mi355x {
 
 void plc_free(LPCNetBatch *b)
 {
-  for (void *p : b->plc_bufs) (void)hipFree(p);
   b->plc_bufs.clear();
   b->plc = {};
   b->plc_ok = false;
@@ -58,22 +67,12 @@ void plc_load(LPCNetBatch *b, const std::vector<Arr> &L)
   }
   PlcArgs a{};
   a.nstreams = b->B;
-  bool ok = true;
-  auto up = [&](const void *src, size_t bytes) -> void * {
-    void *p = nullptr;
-    if (!ok || hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
-    b->plc_bufs.push_back(p);
-    if (src ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(p, 0, bytes) != hipSuccess) ok = false;
-    return p;
-  };
-  for (const ModelUpload &u : plc_uploads(P, a)) {
-    const void *p = up(u.src, u.bytes);
-    memcpy(u.dst, &p, sizeof(p));
-  }
-  a.state = b->plc.state = (float *)up(nullptr, (size_t)b->B * (a.n1 + a.n2) * 4);
-  b->plc.in = (float *)up(nullptr, (size_t)b->B * PLC_IN * 4);
-  b->plc.out = (float *)up(nullptr, (size_t)b->B * NF * 4);
-  b->plc.act = (unsigned char *)up(nullptr, (size_t)b->B);
+  DeviceTables &t = b->plc_bufs;
+  bool ok = t.upload(plc_uploads(P, a)) == 0;
+  ok = ok && (a.state = b->plc.state = (float *)t.zeroed((size_t)b->B * (a.n1 + a.n2) * 4));
+  ok = ok && (b->plc.in = (float *)t.zeroed((size_t)b->B * PLC_IN * 4));
+  ok = ok && (b->plc.out = (float *)t.zeroed((size_t)b->B * NF * 4));
+  ok = ok && (b->plc.act = (unsigned char *)t.zeroed((size_t)b->B));
   if (!ok) {
     plc_free(b);
     b->plc_why = "PLC: device allocation or upload of the predictor tables failed";
@@ -86,9 +85,6 @@ void plc_load(LPCNetBatch *b, const std::vector<Arr> &L)
 
 void feat_free(LPCNetBatch *b)
 {
-  (void)hipFree(b->feat.base);
-  (void)hipFree(b->burg.base);
-  (void)hipFree(b->enc.base);
   b->feat = {};
   b->burg = {};
   b->enc = {};
@@ -96,16 +92,13 @@ void feat_free(LPCNetBatch *b)
 
 int side_reset(LPCNetBatch *b, int stream, int parts)
 {
-  const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)b->B : 1;
-  if ((parts & SIDE_PLC) && b->plc_ok) {
-    const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-    HIPCHK(hipMemsetAsync(b->plc.state + first * nt, 0, n * nt * 4, b->stream));
-  }
+  std::vector<StateRows> rows;
+  if ((parts & SIDE_PLC) && b->plc_ok) rows.push_back(plc_rows_of(b));
   if ((parts & SIDE_FEAT) && b->feat.state) {
-    HIPCHK(hipMemsetAsync(b->feat.state + first, 0, n * sizeof(FeatState), b->stream));
-    if (b->enc.vq) HIPCHK(hipMemsetAsync(b->enc.vq + first * NBANDS, 0, n * NBANDS * 4, b->stream));
+    rows.push_back(feat_rows_of(b));
+    if (b->enc.vq) rows.push_back(vq_rows_of(b));
   }
-  return 0;
+  return rows_zero(rows, stream, b->B, b->stream);
 }
 
 }  // namespace lpcnet_mi355x
@@ -118,7 +111,7 @@ int lpcnet_mi355x::plc_ready(const LPCNetBatch *b)
   return 0;
 }
 
-/* one predictor launch on the batch's stream (timed as which = 2 when timing is on) */
+/* one predictor launch on the batch's stream (timed as TIMED_PLC when timing is on) */
 int lpcnet_mi355x::plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, const unsigned char *d_active)
 {
   PlcArgs a = b->pa;
@@ -127,7 +120,7 @@ int lpcnet_mi355x::plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, c
   a.active = d_active;
   a.rcp = b->fa.rcp;
   a.rcp_hw = b->sa.rcp_hw;
-  return timed_launch(b, 2, b->timing != 0, 1, "plc kernel launch failed", [&] { return launch_plc(a, b->stream); });
+  return timed_launch(b, TIMED_PLC, b->timing != 0, 1, "plc kernel launch failed", [&] { return launch_plc(a, b->stream); });
 }
 
 extern "C" {
@@ -182,10 +175,7 @@ LPCNET_EXPORT int lpcnet_batch_plc_save_state(LPCNetBatch *b, int stream, void *
 {
   if (plc_ready(b) || b->set_device()) return -1;
   if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
-  const size_t nt = (size_t)b->pa.n1 + b->pa.n2;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(buf, b->plc.state + (size_t)stream * nt, nt * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return rows_save({plc_rows_of(b)}, stream, buf, b->stream);
 }
 
 LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, const void *buf)
@@ -199,9 +189,7 @@ LPCNET_EXPORT int lpcnet_batch_plc_restore_state(LPCNetBatch *b, int stream, con
     set_err("PLC snapshot GRU state outside [-2, 2]: not a state this engine produced");
     return -1;
   }
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(b->plc.state + (size_t)stream * nt, buf, nt * 4, hipMemcpyHostToDevice));
-  return 0;
+  return rows_restore({plc_rows_of(b)}, stream, buf, b->stream);
 }
 
 }  // extern "C"
@@ -225,11 +213,10 @@ static int feat_ensure(LPCNetBatch *b)
   f.base = c.alloc();
   if (!f.base || hipMemsetAsync(f.state, 0, sizeof(FeatState) * B, b->stream) != hipSuccess || /* ordered before the first launch */
       hipMemcpy(f.tab, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(f.base);
     set_err("features: device allocation failed");
     return -1;
   }
-  b->feat = f;
+  b->feat = std::move(f);
   return 0;
 }
 
@@ -264,13 +251,13 @@ static FeatArgs feat_args(const LPCNetBatch *b, const short *d_pcm, const float 
   return a;
 }
 
-/* one extractor launch on the batch's stream (timed as which = 3 when timing is on) */
+/* one extractor launch on the batch's stream (timed as TIMED_FEAT when timing is on) */
 int lpcnet_mi355x::feat_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_features, int row,
                                 const unsigned char *d_active, int stride)
 {
   /* stride 0: the dense [B][row] of every call but the predictor rows */
   const FeatArgs a = feat_args(b, d_pcm, d_pcm_f, d_features, row, stride ? stride : row, d_active);
-  return timed_launch(b, 3, b->timing != 0, 1, "feature kernel launch failed", [&] { return launch_feat(a, b->stream); });
+  return timed_launch(b, TIMED_FEAT, b->timing != 0, 1, "feature kernel launch failed", [&] { return launch_feat(a, b->stream); });
 }
 
 static int feat_host(LPCNetBatch *b, const void *pcm, bool is_float, float *features, const unsigned char *active)
@@ -288,7 +275,7 @@ static int feat_host(LPCNetBatch *b, const void *pcm, bool is_float, float *feat
  * contract's order: the stream index and the buffer, a restored snapshot's
  * best_i (the kernel indexes its Viterbi rows with it; restore_of names the
  * snapshot in the error), the batch, the stream against it; then the device,
- * the family's buffers and a quiet stream. */
+ * the family's buffers (the copy that follows waits for the stream). */
 static int snap_ready(LPCNetBatch *b, int stream, const void *buf, const char *restore_of, int (*ensure)(LPCNetBatch *))
 {
   if (stream < 0 || !buf) { set_err(stream < 0 ? "no such stream" : "bad arguments"); return -1; }
@@ -303,19 +290,6 @@ static int snap_ready(LPCNetBatch *b, int stream, const void *buf, const char *r
   if (!b) { set_err("null batch"); return -1; }
   if (stream >= b->B) { set_err("no such stream"); return -1; }
   if (b->set_device() || ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  return 0;
-}
-
-static int feat_state_save(LPCNetBatch *b, int stream, void *buf)
-{
-  HIPCHK(hipMemcpy(buf, b->feat.state + stream, sizeof(FeatState), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-static int feat_state_restore(LPCNetBatch *b, int stream, const void *buf)
-{
-  HIPCHK(hipMemcpy(b->feat.state + stream, buf, sizeof(FeatState), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -362,13 +336,13 @@ LPCNET_EXPORT int lpcnet_batch_features_state_size(const LPCNetBatch *) { return
 LPCNET_EXPORT int lpcnet_batch_features_save_state(LPCNetBatch *b, int stream, void *buf)
 {
   if (snap_ready(b, stream, buf, nullptr, feat_ensure)) return -1;
-  return feat_state_save(b, stream, buf);
+  return rows_save({feat_rows_of(b)}, stream, buf, b->stream);
 }
 
 LPCNET_EXPORT int lpcnet_batch_features_restore_state(LPCNetBatch *b, int stream, const void *buf)
 {
   if (snap_ready(b, stream, buf, "features", feat_ensure)) return -1;
-  return feat_state_restore(b, stream, buf);
+  return rows_restore({feat_rows_of(b)}, stream, buf, b->stream);
 }
 
 }  // extern "C"
@@ -394,15 +368,14 @@ int lpcnet_mi355x::burg_ensure(LPCNetBatch *b)
   build_burg_tables(T);
   g.base = c.alloc();
   if (!g.base || hipMemcpy(g.tab, &T, sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(g.base);
     set_err("burg: device allocation failed");
     return -1;
   }
-  b->burg = g;
+  b->burg = std::move(g);
   return 0;
 }
 
-/* one Burg analysis (its three launches) on the batch's stream, timed as one region, which = 6, when timing is on */
+/* one Burg analysis (its three launches) on the batch's stream, timed as one region, TIMED_BURG, when timing is on */
 int lpcnet_mi355x::burg_launch(LPCNetBatch *b, const short *d_pcm, const float *d_pcm_f, float *d_out, int stride, int fill, float flag,
                                 const unsigned char *d_active)
 {
@@ -421,7 +394,7 @@ int lpcnet_mi355x::burg_launch(LPCNetBatch *b, const short *d_pcm, const float *
   a.cbuf = b->burg.c;
   a.xbuf = b->burg.x;
   a.obuf = b->burg.o;
-  return timed_launch(b, 6, b->timing != 0, 1, "Burg kernel launch failed", [&] { return launch_burg(a, b->stream); });
+  return timed_launch(b, TIMED_BURG, b->timing != 0, 1, "Burg kernel launch failed", [&] { return launch_burg(a, b->stream); });
 }
 
 static int burg_host(LPCNetBatch *b, const void *pcm, bool is_float, float *ceps, const unsigned char *active)
@@ -543,17 +516,16 @@ static int enc_ensure(LPCNetBatch *b)
   if (!n.base || hipMemsetAsync(n.base, 0, c.size(), b->stream) != hipSuccess ||
       hipMemcpyAsync(n.tab, &T, sizeof(T), hipMemcpyHostToDevice, b->stream) != hipSuccess ||
       hipStreamSynchronize(b->stream) != hipSuccess) { /* T leaves scope */
-    (void)hipFree(n.base);
     set_err("encode: device allocation failed");
     return -1;
   }
-  b->enc = n;
+  b->enc = std::move(n);
   return 0;
 }
 
 /* one packet on the batch's stream: d_pcm [4][B][FRAME]; d_packets [B][8] and
- * d_features [4][B][row] may be null.  Timed as which = 4 (and the launches
- * after the analysis as 5) when timing is on. */
+ * d_features [4][B][row] may be null.  Timed as TIMED_ENC (and the launches
+ * after the analysis as TIMED_ENC_KERNEL) when timing is on. */
 static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned char *d_packets, float *d_features, int row,
                       const unsigned char *d_active)
 {
@@ -564,7 +536,7 @@ static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned
     a.xc_out = b->enc.xc;
     a.fw_out = b->enc.fw;
     a.lpc_out = b->enc.lpc + k * B * NLPC;
-    if (timed_launch(b, 4, b->timing != 0, 1, "encoder analysis kernel launch failed", [&] { return launch_feat_super(a, b->stream); }))
+    if (timed_launch(b, TIMED_ENC, b->timing != 0, 1, "encoder analysis kernel launch failed", [&] { return launch_feat_super(a, b->stream); }))
       return -1;
   }
   EncArgs e{};
@@ -603,8 +575,8 @@ static int enc_packet(LPCNetBatch *b, const short *d_pcm, int quantize, unsigned
   }
   if (d_features && launch_enc_out(e, b->stream)) { set_err("encoder output kernel launch failed"); return -1; }
   if (mark(b, e0 != nullptr, b->stream, e1)) return -1;
-  timed(b, 4, e0, e1, 0);
-  timed(b, 5, e0, e1, 4);
+  timed(b, TIMED_ENC, e0, e1, 0);
+  timed(b, TIMED_ENC_KERNEL, e0, e1, 4);
   return 0;
 }
 
@@ -677,16 +649,14 @@ LPCNET_EXPORT int lpcnet_batch_encode_state_size(const LPCNetBatch *) { return (
 /* the features snapshot, then vq_mem */
 LPCNET_EXPORT int lpcnet_batch_encode_save_state(LPCNetBatch *b, int stream, void *buf)
 {
-  if (snap_ready(b, stream, buf, nullptr, enc_ensure) || feat_state_save(b, stream, buf)) return -1;
-  HIPCHK(hipMemcpy((char *)buf + sizeof(FeatState), b->enc.vq + (size_t)stream * NBANDS, NBANDS * 4, hipMemcpyDeviceToHost));
-  return 0;
+  if (snap_ready(b, stream, buf, nullptr, enc_ensure)) return -1;
+  return rows_save({feat_rows_of(b), vq_rows_of(b)}, stream, buf, b->stream);
 }
 
 LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, const void *buf)
 {
-  if (snap_ready(b, stream, buf, "encoder", enc_ensure) || feat_state_restore(b, stream, buf)) return -1;
-  HIPCHK(hipMemcpy(b->enc.vq + (size_t)stream * NBANDS, (const char *)buf + sizeof(FeatState), NBANDS * 4, hipMemcpyHostToDevice));
-  return 0;
+  if (snap_ready(b, stream, buf, "encoder", enc_ensure)) return -1;
+  return rows_restore({feat_rows_of(b), vq_rows_of(b)}, stream, buf, b->stream);
 }
 
 }  // extern "C"
@@ -696,9 +666,7 @@ namespace lpcnet_mi355x {
 
 void rdovae_free(LPCNetBatch *b)
 {
-  for (void *p : b->rdovae_bufs) (void)hipFree(p);
   b->rdovae_bufs.clear();
-  (void)hipFree(b->rdo.base);
   b->rdo = {};
   for (int k = 0; k < 2; k++) {
     b->rdo_ok[k] = false;
@@ -721,14 +689,7 @@ void rdovae_load(LPCNetBatch *b, const std::vector<Arr> &L)
     b->rdo_why[k] = S.why;
     if (!S.ok) continue;
     RdovaeNet n;
-    bool ok = true;
-    for (const ModelUpload &u : rdovae_uploads(S, n)) {
-      void *p = nullptr;
-      if (!ok || hipMalloc(&p, u.bytes) != hipSuccess) { ok = false; break; }
-      b->rdovae_bufs.push_back(p);
-      if (hipMemcpy(p, u.src, u.bytes, hipMemcpyHostToDevice) != hipSuccess) ok = false;
-      memcpy(u.dst, &p, sizeof(p));
-    }
+    const bool ok = b->rdovae_bufs.upload(rdovae_uploads(S, n)) == 0;
     if (ok && rdovae_lds_bytes(n) > 160 * 1024) {
       b->rdo_why[k] = "RDO-VAE: the layer widths need more LDS than a compute unit has";
       continue;
@@ -781,11 +742,10 @@ static int rdovae_ensure(LPCNetBatch *b)
   c.add(r.act, B);
   r.base = c.alloc();
   if (!r.base || hipMemsetAsync(r.base, 0, c.size(), b->stream) != hipSuccess) { /* ordered before the first launch */
-    (void)hipFree(r.base);
     set_err("RDO-VAE: device allocation failed");
     return -1;
   }
-  b->rdo = r;
+  b->rdo = std::move(r);
   return 0;
 }
 
@@ -802,7 +762,7 @@ static RdovaeArgs rdovae_args(const LPCNetBatch *b, int side, const unsigned cha
   return a;
 }
 
-/* one encoder launch on the batch's stream (timed as which = 8 when timing is on) */
+/* one encoder launch on the batch's stream (timed as TIMED_RDOVAE_ENC when timing is on) */
 static int rdovae_enc_launch(LPCNetBatch *b, const float *d_in, size_t in_stream, size_t in_frame, float *d_latents, float *d_state,
                              const unsigned char *d_active)
 {
@@ -818,7 +778,7 @@ static int rdovae_enc_launch(LPCNetBatch *b, const float *d_in, size_t in_stream
                       [&] { return launch_rdovae(a, b->stream); });
 }
 
-/* one decoder launch (which = 9): dec_init from d_init when given, then n
+/* one decoder launch (TIMED_RDOVAE_DEC): dec_init from d_init when given, then n
  * qframes, on the streams' own state or, with `scratch`, on decode_all's */
 static int rdovae_dec_launch(LPCNetBatch *b, const float *d_init, const float *d_lat, float *d_out, int n, bool scratch,
                              const unsigned char *d_active)
@@ -858,6 +818,16 @@ static int rdovae_state_floats(const LPCNetBatch *b, int which, size_t part[3])
   }
   if (which & 2) part[2] = (size_t)b->rdo_net[RDO_DEC].nt;
   return 0;
+}
+
+/* the parts rdovae_state_floats chose, as rows of the batch's buffers */
+static std::vector<StateRows> rdovae_rows(const LPCNetBatch *b, const size_t part[3])
+{
+  float *const base[3] = {b->rdo.enc_state, b->rdo.enc_mem, b->rdo.dec_state};
+  std::vector<StateRows> rows;
+  for (int k = 0; k < 3; k++)
+    if (part[k]) rows.push_back({base[k], part[k] * 4});
+  return rows;
 }
 
 extern "C" {
@@ -957,25 +927,20 @@ LPCNET_EXPORT int lpcnet_batch_rdovae_decode_all(LPCNetBatch *b, const float *st
   if (!state || !latents || !features) { set_err("bad arguments"); return -1; }
   if (b->set_device() || rdovae_ensure(b)) return -1;
   /* a packet's latents and frames: staging of this call's own size */
-  const size_t nl = (size_t)b->B * n * b->rdo_dims[13] * 4, no = (size_t)b->B * n * RDOVAE_QFRAME * 4;
-  float *d_lat = nullptr, *d_out = nullptr;
-  /* everything queued on b->stream; the buffers are freed behind a synchronisation */
-  auto run = [&]() -> int {
-    if (hipMalloc(&d_lat, nl) != hipSuccess || hipMalloc(&d_out, no) != hipSuccess) {
-      set_err("RDO-VAE decode_all: device allocation failed");
-      return -1;
-    }
-    const unsigned char *d_act;
-    if (rdovae_stage(b, b->rdo.st, state, (size_t)b->B * b->rdo_dims[14] * 4, active, d_act)) return -1;
-    HIPCHK(hipMemcpyAsync(d_lat, latents, nl, hipMemcpyHostToDevice, b->stream));
-    if (rdovae_dec_launch(b, b->rdo.st, d_lat, d_out, n, true, d_act)) return -1;
-    return copy_back_active(b, d_out, (size_t)n * RDOVAE_QFRAME * 4, features, active);
-  };
-  const int rc = run();
+  const size_t nl = (size_t)b->B * n * b->rdo_dims[13], no = (size_t)b->B * n * RDOVAE_QFRAME; /* floats */
+  DevPtr<float> d_lat, d_out;
+  if (d_lat.alloc(nl) || d_out.alloc(no)) {
+    set_err("RDO-VAE decode_all: device allocation failed");
+    return -1;
+  }
+  const unsigned char *d_act, *no_mask;
+  const int rc = rdovae_stage(b, b->rdo.st, state, (size_t)b->B * b->rdo_dims[14] * 4, active, d_act) ||
+                 rdovae_stage(b, d_lat, latents, nl * 4, nullptr, no_mask) ||
+                 rdovae_dec_launch(b, b->rdo.st, d_lat, d_out, n, true, d_act) ||
+                 copy_back_active(b, d_out, (size_t)n * RDOVAE_QFRAME * 4, features, active);
+  /* everything was queued on b->stream, and d_lat and d_out go with this call */
   (void)hipStreamSynchronize(b->stream);
-  (void)hipFree(d_lat);
-  (void)hipFree(d_out);
-  return rc;
+  return rc ? -1 : 0;
 }
 
 LPCNET_EXPORT int lpcnet_batch_rdovae_reset(LPCNetBatch *b, int stream, int which)
@@ -985,10 +950,7 @@ LPCNET_EXPORT int lpcnet_batch_rdovae_reset(LPCNetBatch *b, int stream, int whic
   if (stream < -1 || stream >= b->B) { set_err("no such stream"); return -1; }
   if (!b->rdo.base) return 0; /* never used: a first use starts from the reset state */
   if (b->set_device()) return -1;
-  const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)b->B : 1;
-  if (part[0]) HIPCHK(hipMemsetAsync(b->rdo.enc_state + first * part[0], 0, n * part[0] * 4, b->stream));
-  if (part[1]) HIPCHK(hipMemsetAsync(b->rdo.enc_mem + first * part[1], 0, n * part[1] * 4, b->stream));
-  if (part[2]) HIPCHK(hipMemsetAsync(b->rdo.dec_state + first * part[2], 0, n * part[2] * 4, b->stream));
+  if (rows_zero(rdovae_rows(b, part), stream, b->B, b->stream)) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -1006,15 +968,7 @@ LPCNET_EXPORT int lpcnet_batch_rdovae_save_state(LPCNetBatch *b, int stream, int
   if (rdovae_state_floats(b, which, part)) return -1;
   if (stream < 0 || stream >= b->B || !buf) { set_err("bad arguments"); return -1; }
   if (b->set_device() || rdovae_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  const float *src[3] = {b->rdo.enc_state, b->rdo.enc_mem, b->rdo.dec_state};
-  char *out = (char *)buf;
-  for (int k = 0; k < 3; k++) {
-    if (!part[k]) continue;
-    HIPCHK(hipMemcpy(out, src[k] + (size_t)stream * part[k], part[k] * 4, hipMemcpyDeviceToHost));
-    out += part[k] * 4;
-  }
-  return 0;
+  return rows_save(rdovae_rows(b, part), stream, buf, b->stream);
 }
 
 LPCNET_EXPORT int lpcnet_batch_rdovae_restore_state(LPCNetBatch *b, int stream, int which, const void *buf)
@@ -1030,15 +984,7 @@ LPCNET_EXPORT int lpcnet_batch_rdovae_restore_state(LPCNetBatch *b, int stream, 
     return -1;
   }
   if (b->set_device() || rdovae_ensure(b)) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
-  float *dst[3] = {b->rdo.enc_state, b->rdo.enc_mem, b->rdo.dec_state};
-  const float *in = v.data();
-  for (int k = 0; k < 3; k++) {
-    if (!part[k]) continue;
-    HIPCHK(hipMemcpy(dst[k] + (size_t)stream * part[k], in, part[k] * 4, hipMemcpyHostToDevice));
-    in += part[k];
-  }
-  return 0;
+  return rows_restore(rdovae_rows(b, part), stream, v.data(), b->stream);
 }
 
 }  // extern "C"
@@ -1053,11 +999,11 @@ LPCNET_EXPORT int lpcnet_mi355x_device_lpc(int device, const float *cepstra, flo
   if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice failed"); return -1; }
   LpcTables T;
   build_lpc_tables(T);
-  float *dc = nullptr, *dl = nullptr;
-  LpcTables *dt = nullptr;
+  DevPtr<float> dc, dl;
+  DevPtr<LpcTables> dt;
   int rc = -1;
-  if (hipMalloc(&dc, sizeof(float) * NF * (size_t)n) == hipSuccess && hipMalloc(&dl, sizeof(float) * NLPC * (size_t)n) == hipSuccess &&
-      hipMalloc(&dt, sizeof(T)) == hipSuccess && hipMemcpy(dt, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess) {
+  if (dc.alloc(NF * (size_t)n) == 0 && dl.alloc(NLPC * (size_t)n) == 0 && dt.alloc(1) == 0 &&
+      hipMemcpy(dt, &T, sizeof(T), hipMemcpyHostToDevice) == hipSuccess) {
     /* cepstra arrive as [n][NLPC+2] (18 bands); the kernel reads [n][NF] */
     std::vector<float> f((size_t)NF * n, 0.f);
     for (int i = 0; i < n; i++) memcpy(&f[(size_t)i * NF], cepstra + (size_t)i * LPC_NBANDS, sizeof(float) * LPC_NBANDS);
@@ -1065,10 +1011,7 @@ LPCNET_EXPORT int lpcnet_mi355x_device_lpc(int device, const float *cepstra, flo
         hipMemcpy(lpc, dl, sizeof(float) * NLPC * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess)
       rc = 0;
   }
-  if (rc) set_err("device LPC failed");
-  (void)hipFree(dc);
-  (void)hipFree(dl);
-  (void)hipFree(dt);
+  if (rc) set_err("device LPC failed"); /* the blocking copy back has waited for the kernel */
   return rc;
 }
 

@@ -179,8 +179,8 @@ int launch_frame_step(LPCNetBatch *b, const FrameStep &s)
     }
     b->ev_samp_used[c] = true;
   }
-  timed(b, 1, e0, ef ? ef : e1, 1);
-  timed(b, 0, e1, e2, 1);
+  timed(b, TIMED_FRAME, e0, ef ? ef : e1, 1);
+  timed(b, TIMED_SAMPLE, e1, e2, 1);
   if (run_frame && own) b->frames_done(1);
   return 0;
 }
@@ -197,7 +197,7 @@ int launch_chunk_samples(LPCNetBatch *b, int f, short *d_pcm, int N, int nfr = 1
   sa.nframes = nfr;
   sa.pcm = d_pcm;
   sa.stamps = b->d_stamps;
-  return timed_launch(b, 0, b->timing >= 1, nfr, nullptr, [&] { return launch_sample_kernel(b, sa); });
+  return timed_launch(b, TIMED_SAMPLE, b->timing >= 1, nfr, nullptr, [&] { return launch_sample_kernel(b, sa); });
 }
 
 /* Chunked form: the frame network of n frames (features [n][B][NF], their
@@ -208,7 +208,7 @@ int launch_chunk_frames(LPCNetBatch *b, const float *d_features, int n)
   fa.nframes = n;
   fa.cond = b->d_chunk;
   fa.stamps = nullptr;
-  if (timed_launch(b, 1, b->timing >= 2, n, "chunk kernel launch failed", [&] { return launch_chunk(fa, b->stream); })) return -1;
+  if (timed_launch(b, TIMED_FRAME, b->timing >= 2, n, "chunk kernel launch failed", [&] { return launch_chunk(fa, b->stream); })) return -1;
   b->frames_done(n);
   return 0;
 }
@@ -266,8 +266,8 @@ static int launch_single_frame_chunked(LPCNetBatch *b, int nB, const float *d_fe
   if (mark(b, b->timing >= 1, b->stream, e1)) return -1;
   if (launch_sample_kernel(b, sa)) return -1;
   if (mark(b, b->timing >= 1, b->stream, e2)) return -1;
-  timed(b, 1, e0, e1, 1);
-  timed(b, 0, e1, e2, 1);
+  timed(b, TIMED_FRAME, e0, e1, 1);
+  timed(b, TIMED_SAMPLE, e1, e2, 1);
   return 0;
 }
 
@@ -285,23 +285,21 @@ static int ensure_host_io(LPCNetBatch *b)
     int large_bar = 0;
     (void)hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, b->device);
     const char *ev = getenv("LPCNET_FEAT_VRAM");
-    if (large_bar && !(ev && atoi(ev) == 0) &&
-        hipExtMallocWithFlags((void **)&b->h_io_feat, sizeof(float) * NF * (size_t)b->B, hipDeviceMallocFinegrained) ==
-            hipSuccess) {
+    if (large_bar && !(ev && atoi(ev) == 0) && b->io_feat_dev.alloc_finegrained(NF * (size_t)b->B) == 0) {
       b->io_feat_vram = true;
-      b->d_io_feat = b->h_io_feat;
+      b->h_io_feat = b->d_io_feat = b->io_feat_dev;
     } else {
-      b->h_io_feat = nullptr;
-      HIPCHK(hipHostMalloc(&b->h_io_feat, sizeof(float) * NF * (size_t)b->B, hipHostMallocMapped));
-      HIPCHK(hipHostGetDevicePointer((void **)&b->d_io_feat, b->h_io_feat, 0));
+      if (b->io_feat_host.alloc(NF * (size_t)b->B, true)) return -1;
+      HIPCHK(hipHostGetDevicePointer((void **)&b->d_io_feat, b->io_feat_host, 0));
+      b->h_io_feat = b->io_feat_host;
     }
   }
   if (!b->h_io_pcm) {
-    HIPCHK(hipHostMalloc(&b->h_io_pcm, sizeof(short) * FRAME * (size_t)b->B, hipHostMallocMapped));
+    if (b->h_io_pcm.alloc(FRAME * (size_t)b->B, true)) return -1;
     HIPCHK(hipHostGetDevicePointer((void **)&b->d_io_pcm, b->h_io_pcm, 0));
   }
-  if (!b->h_stg_feat) HIPCHK(hipHostMalloc(&b->h_stg_feat, sizeof(float) * NF * (size_t)b->B, hipHostMallocDefault));
-  if (!b->h_stg_pcm) HIPCHK(hipHostMalloc(&b->h_stg_pcm, sizeof(short) * FRAME * (size_t)b->B, hipHostMallocDefault));
+  if (!b->h_stg_feat && b->h_stg_feat.alloc(NF * (size_t)b->B, false)) return -1;
+  if (!b->h_stg_pcm && b->h_stg_pcm.alloc(FRAME * (size_t)b->B, false)) return -1;
   return 0;
 }
 
@@ -320,7 +318,7 @@ static int tick_sync(LPCNetBatch *b, bool poll, const std::function<int()> &afte
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
   }
-  if (!b->ev_tick) HIPCHK(hipEventCreateWithFlags(&b->ev_tick, hipEventDisableTiming));
+  if (!b->ev_tick && b->ev_tick.create(false)) return -1;
   HIPCHK(hipEventRecord(b->ev_tick, b->stream));
   /* work queued behind the tick's end (the deferred LPC): not waited for */
   if (after && after()) return -1;
@@ -449,9 +447,9 @@ LPCNET_EXPORT short *lpcnet_batch_host_pcm(LPCNetBatch *b)
 
 static int ensure_decode_bufs(LPCNetBatch *b, bool host_io)
 {
-  if (!b->d_packets) HIPCHK(hipMalloc(&b->d_packets, (size_t)DEC_MAX_PACKETS * b->B * 8));
-  if (!b->d_dfeat) HIPCHK(hipMalloc(&b->d_dfeat, sizeof(float) * NF * 4 * DEC_MAX_PACKETS * (size_t)b->B));
-  if (host_io && !b->d_dpcm) HIPCHK(hipMalloc(&b->d_dpcm, sizeof(short) * 4 * FRAME * (size_t)b->B));
+  if (!b->d_packets && b->d_packets.alloc((size_t)DEC_MAX_PACKETS * b->B * 8)) return -1;
+  if (!b->d_dfeat && b->d_dfeat.alloc((size_t)NF * 4 * DEC_MAX_PACKETS * b->B)) return -1;
+  if (host_io && !b->d_dpcm && b->d_dpcm.alloc((size_t)4 * FRAME * b->B)) return -1;
   return 0;
 }
 
@@ -640,8 +638,7 @@ LPCNET_EXPORT int lpcnet_batch_synthesize_frames(LPCNetBatch *b, const float *h_
     /* frame-network outputs of a chunk of frames (chunk_kernel -> sample
      * launches): sizeof(FrameCond) = 4.9 KB x LPC_CHUNK per stream (160 MB
      * at 1024 streams), only for batches that take this path */
-    if (hipMalloc(&b->d_chunk, sizeof(FrameCond) * (size_t)LPC_CHUNK * b->B) != hipSuccess) {
-      b->d_chunk = nullptr;
+    if (b->d_chunk.alloc((size_t)LPC_CHUNK * b->B)) {
       set_err("device allocation of the chunked frame-network buffer failed");
       return -1;
     }
