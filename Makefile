@@ -16,7 +16,7 @@ JOBS ?= 4
 BUILD := build
 LIB := lpcnet_amd/liblpcnet_mi355x.so
 CSRC := lpcnet_amd/csrc
-HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/gru_tile.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/device_mem.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h $(CSRC)/conceal_plan.h
+HDRS := include/lpcnet.h include/lpcnet_mi355x.h $(CSRC)/lpcnet_engine.h $(CSRC)/side_kernels.h $(CSRC)/device_math.h $(CSRC)/sampler.h $(CSRC)/lds_flags.h $(CSRC)/mf_common.h $(CSRC)/gru_tile.h $(CSRC)/l2_warm.h $(CSRC)/pow10_dd.h $(CSRC)/lpc_stages.h $(CSRC)/rcp_table_x86.inc $(CSRC)/mf_plan.h $(CSRC)/model_host.h $(CSRC)/side_tables.h $(CSRC)/device_mem.h $(CSRC)/batch.h $(CSRC)/pool_combiner.h $(CSRC)/kernel_choice.h $(CSRC)/conceal_plan.h
 EXTRA ?=
 COMMON := $(EXTRA) -O3 -fPIC -ffp-contract=off -fno-fast-math -std=c++17 -Iinclude -I$(CSRC) -fvisibility=hidden -Wall -Wno-unused-function
 OBJS := $(BUILD)/kernels.o $(BUILD)/mf_kernel.o $(BUILD)/mf2_kernel.o $(BUILD)/fp_kernel.o $(BUILD)/selftest.o $(BUILD)/frame_kernel.o $(BUILD)/engine.o $(BUILD)/device_mem.o $(BUILD)/synth_steps.o $(BUILD)/lpc_kernel.o $(BUILD)/chunk_kernel.o $(BUILD)/model_gen.o $(BUILD)/host_rcpps.o $(BUILD)/decode_kernel.o $(BUILD)/mfw_kernel.o $(BUILD)/plc_kernel.o $(BUILD)/rdovae_kernel.o $(BUILD)/feat_kernel.o $(BUILD)/burg_kernel.o $(BUILD)/enc_kernel.o $(BUILD)/mf_plan.o $(BUILD)/model_host.o $(BUILD)/dropin.o $(BUILD)/pool_combiner.o $(BUILD)/kernel_choice.o $(BUILD)/side_tables.o $(BUILD)/side_calls.o $(BUILD)/conceal_kernel.o $(BUILD)/conceal_calls.o $(BUILD)/conceal_plan.o

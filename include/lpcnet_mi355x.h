@@ -311,8 +311,8 @@ LPCNET_EXPORT int lpcnet_mi355x_device_numerics(int device, int op, const void *
 LPCNET_EXPORT int lpcnet_mi355x_validate_model(const unsigned char *data, int len);
 /* Host-only digests of everything a load of the blob would hand a batch of
  * `streams` streams: one FNV-1a-64 per entry, in this order:
- *   [0]      the sample kernels' argument block (scalars; its device
- *            pointers null);
+ *   [0]      the sample kernels' scalars of every family (their table
+ *            offsets, group counts, bounds and forms) as one block;
  *   [1..56]  the device tables, as uploaded: the frame network's conv1_w,
  *            conv1_b, conv2_w, conv2_b, dense1_w, dense1_b, dense2_w,
  *            dense2_b, gadf_w, gadf_b, gbdf_w, gbdf_b, proj_w, proj_b,

@@ -27,6 +27,7 @@
 #include "lpcnet_engine.h"
 #include "lpcnet_mi355x.h"
 #include "model_host.h"
+#include "side_kernels.h"
 #include "side_tables.h"
 
 /* LPCNetBatch is the C API's type, outside the namespace its fields come from */
@@ -164,7 +165,7 @@ struct LPCNetBatch {
   LPCNetModelInfo info{};
   DeviceTables model_bufs;
   FrameArgs fa{};
-  SampleArgs sa{};
+  SampleTables sample{}; /* the sample kernels' model side, device pointers set (load_model) */
   /* streams */
   DevPtr<StreamState> d_state;
   DevPtr<float> d_feat;
@@ -200,6 +201,8 @@ struct LPCNetBatch {
   bool trace = false;
   DevPtr<float> d_trace_logits; /* both or neither (ensure_trace) */
   DevPtr<int> d_trace_exc;
+  float *trace_logits = nullptr; /* what the sample launches write: the two buffers above */
+  int *trace_exc = nullptr;      /* (ensure_trace), or null */
   int trace_N = 0;
   /* device -> host status word (pinned, mapped): a kernel that aborts sets
    * STATUS_* bits; every synchronising entry point checks and clears it */
@@ -269,8 +272,8 @@ bool gru_state_plausible(const float *v, size_t n);
 int mark(LPCNetBatch *b, bool on, hipStream_t s, hipEvent_t &e);
 void timed(LPCNetBatch *b, int which, hipEvent_t e0, hipEvent_t e1, int frames);
 /* engine.cpp.  ensure_trace: before the sample launches of a call of N samples
- * per frame, the batch's trace buffers (allocated here, both or neither) in
- * b->sa, or none.
+ * per frame, the batch's trace buffers (allocated here, both or neither) as
+ * the launches' trace targets (b->trace_logits, b->trace_exc), or none.
  * check_status: after a sync of b->stream, report (set_err, -1) and clear a
  * device-side abort. */
 int ensure_trace(LPCNetBatch *b, int N);

@@ -39,7 +39,7 @@
  */
 #include <hip/hip_runtime.h>
 
-#include "lpcnet_engine.h"
+#include "side_kernels.h"
 #include "lpc_stages.h"
 
 namespace lpcnet_mi355x {

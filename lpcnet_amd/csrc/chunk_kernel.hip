@@ -35,6 +35,7 @@
 
 #include "device_math.h"
 #include "lpcnet_engine.h"
+#include "side_kernels.h" /* LPC_CHUNK */
 
 namespace lpcnet_mi355x {
 

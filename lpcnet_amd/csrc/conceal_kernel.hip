@@ -13,7 +13,7 @@
  */
 #include <hip/hip_runtime.h>
 
-#include "lpcnet_engine.h"
+#include "side_kernels.h"
 
 namespace lpcnet_mi355x {
 

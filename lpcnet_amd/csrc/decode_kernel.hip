@@ -21,7 +21,7 @@
  * is the one transcendental; its 64 possible values come from the host
  * (model_host.cpp), computed with the reference's own expression.
  */
-#include "lpcnet_engine.h"
+#include "side_kernels.h"
 
 namespace lpcnet_mi355x {
 

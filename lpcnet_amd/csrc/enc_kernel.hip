@@ -34,7 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
-#include "lpcnet_engine.h"
+#include "side_kernels.h"
 #include "lpc_stages.h"
 
 namespace lpcnet_mi355x {

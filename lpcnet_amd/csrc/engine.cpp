@@ -127,8 +127,8 @@ ModelCaps model_caps(const HostModel &h)
   ModelCaps c;
   c.fp_ok = h.fp_ok;
   c.mf_ok = h.mf_ok;
-  c.mf_split = h.sa.mf_split != 0;
-  c.mfw_split = h.sa.mfw_split != 0;
+  c.mf_split = h.sample.form.mf_split != 0;
+  c.mfw_split = h.sample.form.mfw_split != 0;
   c.reg = h.reg;
   c.S = h.S;
   c.lds_bytes = h.lds;
@@ -161,7 +161,7 @@ void plan_batch(LPCNetBatch *b)
 {
   b->plan = plan_sample_kernels(b->caps, lds_sizes(b->caps), b->B, current_device_cus(), b->kernel_mode, b->rcp_custom,
                                 choice_env_from_env());
-  b->sa.rcp_hw = b->fa.rcp_hw = b->plan.rcp_hw;
+  b->sample.form.rcp_hw = b->fa.rcp_hw = b->plan.rcp_hw;
   b->info.rcp_hw = b->plan.rcp_hw;
   b->info.quad_path = b->plan.quad_path;
   b->info.streams_per_workgroup = b->plan.streams_per_workgroup;
@@ -216,7 +216,7 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, HostModel &ho
    * here, and nothing below can fail: every check passed and the last upload
    * succeeded. */
   b->model_bufs = std::move(bufs); /* frees a replan's previous tables */
-  b->sa = args.sa;
+  b->sample = args.sample;
   b->fa = args.fa;
   b->da = args.da;
   b->has_codebooks = host.cb_ok;
@@ -240,15 +240,55 @@ int load_model(LPCNetBatch *b, const unsigned char *data, int len, HostModel &ho
   return 0;
 }
 
+/* Entry 0 of a model digest: the sample kernels' scalars of every family in
+ * the one byte layout tests/golden/model_digests.json was recorded with --
+ * the launch fields zero, a null pointer where a table's address goes.  A
+ * fixture of this layout compares every scalar a load computes with the
+ * commit that recorded it, however the kernels' arguments are grouped. */
+struct DigestScalars {
+  void *st; int delay; void *cond; int nstreams, N, nframes; void *pcm; int preload;
+  void *emb[3], *ga_par, *ga_wsum, *gb_par, *gb_wsum, *image;
+  int image_bytes, image_lds_bytes;
+  int ga_K[SAMPLE_WAVES][3], ga_woff[SAMPLE_WAVES][3], ga_coff[SAMPLE_WAVES][3];
+  int gb_nb[GB_ROWS / 8], gb_woff[GB_ROWS / 8], gb_coff[GB_ROWS / 8], gb_rec_off;
+  int ga_K4[SAMPLE_WAVES][3], ga_qoff[SAMPLE_WAVES][3], gb_qoff[GB_ROWS / 8];
+  void *mf, *mf_unit; float mf_zr_bound, mf_h_bound; int fc_fin; void *mf_emb[3];
+  int mf_nzr[SAMPLE_WAVES], mf_nh[SAMPLE_WAVES], mf_split, mf_nfzr[SAMPLE_WAVES], mf_nfh[SAMPLE_WAVES]; void *mf_frow;
+  int mfw_split; void *mfw_tab, *mfw_frow, *mfw_unit, *mfw_emb[3];
+  int mfw_nzr[MFW_TAB_WAVES], mfw_nh[MFW_TAB_WAVES]; void *mf_gb;
+  void *fp_zr, *fp_h, *fp_gb, *fp_off; int fp_nzr[SAMPLE_WAVES], fp_nh[SAMPLE_WAVES];
+  int fp_long, fpl_kz, fpl_kh; void *fpl_zr, *fpl_h, *fpl_off;
+  void *ga_wf, *gb_wf, *gb_recf;
+  void *stamps, *trace_logits, *trace_exc; int rcp_hw; void *status; int spin_limit;
+};
+
+uint64_t digest_scalars(const SampleTables &t)
+{
+  DigestScalars d;
+  memset(&d, 0, sizeof(d));
+#define COPY(part, m) memcpy(&d.m, &t.part.m, sizeof(d.m)); static_assert(sizeof(d.m) == sizeof(t.part.m), #m)
+  COPY(lockstep, image_bytes); COPY(lockstep, image_lds_bytes);
+  COPY(lockstep, ga_K); COPY(lockstep, ga_woff); COPY(lockstep, ga_coff);
+  COPY(lockstep, gb_nb); COPY(lockstep, gb_woff); COPY(lockstep, gb_coff); COPY(lockstep, gb_rec_off);
+  COPY(lockstep, ga_K4); COPY(lockstep, ga_qoff); COPY(lockstep, gb_qoff);
+  COPY(mf, mf_zr_bound); COPY(mf, mf_h_bound); COPY(mf, fc_fin);
+  COPY(mf, mf_nzr); COPY(mf, mf_nh); COPY(mf, mf_nfzr); COPY(mf, mf_nfh);
+  COPY(mfw, mfw_nzr); COPY(mfw, mfw_nh);
+  COPY(fp, fp_nzr); COPY(fp, fp_nh); COPY(fp, fpl_kz); COPY(fp, fpl_kh);
+  COPY(form, mf_split); COPY(form, mfw_split); COPY(form, fp_long); COPY(form, rcp_hw);
+#undef COPY
+  return fnv1a64(&d, sizeof(d));
+}
+
 }  // namespace
 
 /* Before the sample launches of a call (batch.h): the batch's trace buffers
- * in its sample arguments, or none. */
+ * as its sample launches' trace targets, or none. */
 int lpcnet_mi355x::ensure_trace(LPCNetBatch *b, int N)
 {
   if (!b->trace) {
-    b->sa.trace_logits = nullptr;
-    b->sa.trace_exc = nullptr;
+    b->trace_logits = nullptr;
+    b->trace_exc = nullptr;
     return 0;
   }
   if (!b->d_trace_logits) {
@@ -259,8 +299,8 @@ int lpcnet_mi355x::ensure_trace(LPCNetBatch *b, int N)
     b->d_trace_logits = std::move(logits);
     b->d_trace_exc = std::move(exc);
   }
-  b->sa.trace_logits = b->d_trace_logits;
-  b->sa.trace_exc = b->d_trace_exc;
+  b->trace_logits = b->d_trace_logits;
+  b->trace_exc = b->d_trace_exc;
   b->trace_N = N;
   return 0;
 }
@@ -547,7 +587,7 @@ LPCNET_EXPORT int lpcnet_batch_set_rcp_table(LPCNetBatch *b, const uint32_t *tab
   if (b->set_device()) return -1;
   HIPCHK(hipStreamSynchronize(b->stream));
   /* the LDS image's table section and the frame network's global copy */
-  HIPCHK(hipMemcpy((unsigned char *)b->sa.image + IMG_RCP, dev.data(), RCP_ENTRIES * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((unsigned char *)b->sample.model.image + IMG_RCP, dev.data(), RCP_ENTRIES * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy((void *)b->fa.rcp, dev.data(), RCP_ENTRIES * 4, hipMemcpyHostToDevice));
   b->rcp_dev = dev;
   b->rcp_custom = dev != dflt;
@@ -797,8 +837,8 @@ LPCNET_EXPORT int lpcnet_mi355x_validate_model(const unsigned char *data, int le
   return build_host_model(data, len, build_opts(B, wide_now(B, 0, false, current_device_cus())), host);
 }
 
-/* fixed order: the SampleArgs block, the MODEL_TABLES upload entries (0: not
- * part of this model), ck_rep, the kernel-choice scalars, the work numbers */
+/* fixed order: the sample kernels' scalars, the MODEL_TABLES upload entries (0:
+ * not part of this model), ck_rep, the kernel-choice scalars, the work numbers */
 LPCNET_EXPORT int lpcnet_mi355x_model_digest(const unsigned char *data, int len, int streams, int cus, int wide, uint64_t *out,
                                              int cap)
 {
@@ -807,7 +847,7 @@ LPCNET_EXPORT int lpcnet_mi355x_model_digest(const unsigned char *data, int len,
   if (build_host_model(data, len, build_opts(streams, wide < 0 ? wide_now(streams, 0, false, cus) : wide != 0), h)) return -1;
   ModelArgs args;
   int n = 0;
-  out[n++] = fnv1a64(&h.sa, sizeof(h.sa));
+  out[n++] = digest_scalars(h.sample);
   for (const ModelUpload &u : model_uploads(h, args)) out[n++] = u.present ? fnv1a64(u.src, u.bytes) : 0;
   out[n++] = fnv1a64(h.ck_rep, sizeof(h.ck_rep));
   const int sc[] = {h.variant, h.sat, h.reg, h.mf_ok, h.fp_ok, h.cb_ok, h.plan_wide, h.rcp_custom, h.S, h.lds, h.nba, h.nbb};

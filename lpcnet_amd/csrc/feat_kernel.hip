@@ -24,7 +24,7 @@
  */
 #include <hip/hip_runtime.h>
 
-#include "lpcnet_engine.h"
+#include "side_kernels.h"
 #include "lpc_stages.h"
 
 namespace lpcnet_mi355x {

@@ -259,7 +259,7 @@ __device__ __forceinline__ float h_chain_stream(const float4 *hw /* lane's slot 
 /* DIAG: 0 the production kernel, 1 with the logit / excitation trace, 2
  * with the s_memtime phase stamps (mf_kernel.hip) */
 template <int DIAG, bool LONG, bool HWR>
-__global__ __launch_bounds__(FP_THREADS) void fp_kernel(SampleArgs A)
+__global__ __launch_bounds__(FP_THREADS) void fp_kernel(FpArgs A)
 {
   constexpr bool TRACE = DIAG == 1;
   extern __shared__ uint4 lds4[];
@@ -642,24 +642,24 @@ __global__ __launch_bounds__(FP_THREADS) void fp_kernel(SampleArgs A)
 }
 
 template <int DIAG, bool LONG, bool HWR = true>
-static int launch_fp_t(const SampleArgs &a, hipStream_t stream)
+static int launch_fp_t(const FpArgs &a, hipStream_t stream)
 {
   if (ensure_dyn_lds((const void *)fp_kernel<DIAG, LONG, HWR>, 160 * 1024 - IMG_VAR)) return -1;
   hipLaunchKernelGGL((fp_kernel<DIAG, LONG, HWR>), dim3(warm_grid(a.nstreams, a.nstreams)), dim3(FP_THREADS), fp_lds_bytes() - IMG_VAR, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_fp(const SampleArgs &a, void *stream)
+int launch_fp(const FpArgs &a, const SampleForm &f, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
-  if (!a.rcp_hw) {
+  if (!f.rcp_hw) {
     /* another host's rcpps table: every activation through it (production
      * and trace forms; no stamped build) */
     if (a.stamps) return -1;
-    if (a.fp_long) return a.trace_logits ? launch_fp_t<1, true, false>(a, st) : launch_fp_t<0, true, false>(a, st);
+    if (f.fp_long) return a.trace_logits ? launch_fp_t<1, true, false>(a, st) : launch_fp_t<0, true, false>(a, st);
     return a.trace_logits ? launch_fp_t<1, false, false>(a, st) : launch_fp_t<0, false, false>(a, st);
   }
-  if (a.fp_long)
+  if (f.fp_long)
     return a.trace_logits ? launch_fp_t<1, true>(a, st) : a.stamps ? launch_fp_t<2, true>(a, st) : launch_fp_t<0, true>(a, st);
   return a.trace_logits ? launch_fp_t<1, false>(a, st) : a.stamps ? launch_fp_t<2, false>(a, st) : launch_fp_t<0, false>(a, st);
 }

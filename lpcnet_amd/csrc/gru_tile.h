@@ -8,7 +8,7 @@
  * product, K = units), each seeded from its half of subias, so lane l ends
  * with all six sums of units 16 ut + 4 (l / 16) + 0..3 of stream l % 16 and
  * runs their elementwise step in registers, in the C order of nnet.c:362-371.
- * The weights are the A tiles and seeds of lpcnet_engine.h PlcArgs; x rows
+ * The weights are the A tiles and seeds of side_kernels.h PlcArgs; x rows
  * are LDS bytes [stream][K + 16] (u8 ^ 0x80).  The caller puts a workgroup
  * barrier before (the rows are complete) and after (the outputs are).
  */
@@ -16,6 +16,7 @@
 #define LPCNET_GRU_TILE_H
 
 #include "mf_common.h"
+#include "side_kernels.h" /* PlcArgs, PLC_THREADS */
 
 namespace lpcnet_mi355x {
 

@@ -131,7 +131,7 @@ FramePath frame_path(const SamplePlan &plan, int B, bool has_fstream, bool chunk
   /* the kernels reading the frame outputs through FrameCond */
   const bool cond = mf || plan.base == SampleKernel::FP;
   FramePath fp;
-  /* multi-frame matrix-core sample launches (SampleArgs::nframes): one
+  /* multi-frame matrix-core sample launches (SampleLaunch::nframes): one
    * launch per chunk instead of one per frame (each costs a ~10 us dispatch
    * gap plus its prologue), behind the chunked frame network */
   fp.multi_frame = mf && chunking && !trace && N > 0 && nframes >= CHUNK_MIN_FRAMES && !env.no_multiframe;

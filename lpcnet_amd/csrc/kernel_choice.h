@@ -75,7 +75,7 @@ struct SamplePlan {
   bool mfw_forced = false; /* LPCNET_MFW=1: mfw_kernel for every launch, however narrow */
   int mfw_g = 3;           /* mfw_kernel's four-stream groups per workgroup (2 or 3) */
   int cus = 256;           /* compute units of the batch's device */
-  int rcp_hw = 1;          /* SampleArgs / FrameArgs::rcp_hw: 0 with a custom rcpps table */
+  int rcp_hw = 1;          /* SampleForm / FrameArgs::rcp_hw: 0 with a custom rcpps table */
   /* LPCNetModelInfo */
   int quad_path = 0, streams_per_workgroup = 1, lds_bytes = 0;
   double mfma_ops_per_group_sample = 0;

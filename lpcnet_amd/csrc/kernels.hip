@@ -170,7 +170,7 @@ __device__ __forceinline__ void gru_a_stream(const unsigned char *xa, const uint
 }
 
 template <int S, int V, bool SAT, bool REG>
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs A)
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(LockstepArgs A)
 {
   extern __shared__ uint4 lds4[];
   unsigned char *lds = (unsigned char *)lds4;
@@ -642,7 +642,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs A)
 }
 
 template <int S, int V, bool SAT, bool REG>
-static int launch_sample_t(const SampleArgs &a, int lds_bytes, hipStream_t stream)
+static int launch_sample_t(const LockstepArgs &a, int lds_bytes, hipStream_t stream)
 {
   if (ensure_dyn_lds((const void *)sample_kernel<S, V, SAT, REG>, 160 * 1024)) return -1;
   int grid = (a.nstreams + S - 1) / S;
@@ -651,14 +651,14 @@ static int launch_sample_t(const SampleArgs &a, int lds_bytes, hipStream_t strea
 }
 
 template <int S>
-static int launch_s(const SampleArgs &a, int variant, int sat, int reg, int lds_bytes, hipStream_t st)
+static int launch_s(const LockstepArgs &a, int variant, int sat, int reg, int lds_bytes, hipStream_t st)
 {
   if (variant == 1) return launch_sample_t<S, 1, false, false>(a, lds_bytes, st);
   if (sat) return reg ? launch_sample_t<S, 0, true, true>(a, lds_bytes, st) : launch_sample_t<S, 0, true, false>(a, lds_bytes, st);
   return reg ? launch_sample_t<S, 0, false, true>(a, lds_bytes, st) : launch_sample_t<S, 0, false, false>(a, lds_bytes, st);
 }
 
-int launch_sample(const SampleArgs &a, int S, int variant, int sat, int reg, int lds_bytes, void *stream)
+int launch_sample(const LockstepArgs &a, int S, int variant, int sat, int reg, int lds_bytes, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
   if (S == 4) return launch_s<4>(a, variant, sat, reg, lds_bytes, st);

@@ -20,7 +20,7 @@ __device__ __forceinline__ int flag_load(const int *p)
 /* Spin until *p >= v.  A wait that outlives `limit` polls (a bug, never a
  * legal schedule) sets the workgroup's abort word, after which every wait
  * returns at once: the kernel finishes instead of hanging the device, and
- * reports the abort through SampleArgs::status (the host call returns -1). */
+ * reports the abort through SampleLaunch::status (the host call returns -1). */
 /* SLEEP > 0: s_sleep between polls (64 clocks per unit) -- for long waits,
  * so idle waves do not flood the LDS the working waves depend on. */
 template <int SLEEP = 0>

@@ -15,7 +15,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "lpcnet_engine.h"
+#include "side_kernels.h"
 #include "pow10_dd.h"
 
 namespace lpcnet_mi355x {

@@ -1,6 +1,10 @@
 /*
- * lpcnet_engine.h -- internal declarations of the MI355X LPCNet engine.
- * Shared by the host engine (engine.cpp) and the HIP kernels (kernels.hip).
+ * lpcnet_engine.h -- the synthesis path's internal declarations: the model
+ * dimensions, a stream's state, the frame step's arguments and outputs, and
+ * the sample kernels' arguments and launchers.  Shared by the frame and
+ * sample kernels (.hip), the host code that fills their arguments
+ * (model_host.cpp, engine.cpp, synth_steps.cpp) and, for the dimensions and
+ * StreamState, the kernels beside synthesis (side_kernels.h).
  */
 #ifndef LPCNET_ENGINE_H
 #define LPCNET_ENGINE_H
@@ -170,7 +174,7 @@ struct FrameArgs {
    * run_frame_network_flush does (lpcnet.c:134-144): conv memories, LPC ring
    * and frame_count advance, the state's conditioning and lpc stay */
   int keep_cond;
-  int rcp_hw; /* chunk_kernel: hardware-reciprocal tanh allowed (see SampleArgs::rcp_hw) */
+  int rcp_hw; /* chunk_kernel: hardware-reciprocal tanh allowed (see SampleForm::rcp_hw) */
   /* chunk_kernel: the same five weight matrices re-tiled for 16-byte
    * per-lane loads (ck_tile_weights): [row tile][k quad][64 lanes] float4,
    * lane l = (g, r) = (l / 16, l % 16), element j of quad q = W[4 (4q + j) +
@@ -195,7 +199,15 @@ struct FrameArgs {
 constexpr int CK_SLICES_MAX = 4; /* projection slices of the one-frame chunk kernel */
 constexpr int CK_WPAD = 8; /* chunk_kernel: k quads in flight per wave (zero padding of each row tile) */
 
-struct SampleArgs {
+/* ---- The sample kernels' arguments, by owner.  Every sample kernel takes
+ * one aggregate by value: what the launch sets (SampleLaunch), what every
+ * kernel family reads of a model (SampleModel) and its own family's tables.
+ * A loaded model keeps the model part and each family's tables with their
+ * device pointers set (model_host.h ModelArgs, batch.h); synth_steps.cpp
+ * builds the launch part per launch. ---- */
+
+/* What one launch sets (synth_steps.cpp sample_args and its callers). */
+struct SampleLaunch {
   StreamState *st;
   int delay;             /* FEATURES_DELAY: a stream synthesises once frame_count > delay (lpcnet.c:239) */
   const FrameCond *cond; /* optional [B]: read the frame's outputs here instead of st */
@@ -207,20 +219,36 @@ struct SampleArgs {
                             at the `delay` transition, STATUS_ACTIVITY otherwise) */
   short *pcm;            /* [B][N] */
   int preload;           /* samples 0..preload-1 are teacher-forced from pcm (lpcnet.c:256-259) */
-  const float *emb_sig, *emb_pred, *emb_exc; /* [256][GA_ROWS] */
+  unsigned long long *stamps; /* optional diagnostics [grid][STAMP_WAVES][16] s_memtime sums */
+  float *trace_logits;   /* optional [B][N][8] */
+  int *trace_exc;        /* optional [B][N] */
+  int *status;           /* device view of the batch's pinned status word: a
+                            kernel that aborts sets bits (STATUS_*), the host
+                            checks after every sync */
+  int spin_limit;        /* polls before an LDS flag wait aborts (FLAG_SPIN_LIMIT_DEFAULT) */
+};
+
+/* What more than one kernel family reads of a model. */
+struct SampleModel {
+  const float *emb_sig, *emb_pred, *emb_exc; /* [256][GA_ROWS] (lockstep, fp) */
   const float *ga_par;   /* [6][NA]: recurrent bias z,r,h then diag z,r,h */
   const int *ga_wsum;    /* [3][NA]: 128*rowsum(int8 w) (non-saturating int8 path) */
   const float *gb_par;   /* [2][GB_ROWS]: input bias, recurrent bias */
   const int *gb_wsum;    /* [2][GB_ROWS] */
-  const uint4 *image;    /* LDS image */
+  const uint4 *image;    /* LDS image: every kernel reads its fixed sections (IMG_*) */
+  const float *gb_recf;  /* fp32 variant: GRU_B recurrent [NB][GB_ROWS] (lockstep, fp) */
+};
+
+/* The lockstep kernel (kernels.hip): where its weights lie in the image. */
+struct LockstepTables {
   int image_bytes;
-  int image_lds_bytes;   /* lockstep kernel: bytes of the image copied to LDS (image_bytes, or IMG_VAR
+  int image_lds_bytes;   /* bytes of the image copied to LDS (image_bytes, or IMG_VAR
                             when the weight sections stay in global memory) */
   int ga_K[SAMPLE_WAVES][3];   /* blocks per lane for wave w, gate g (padded) */
   int ga_woff[SAMPLE_WAVES][3];/* weight chunk offset (u32 units in image / float4 units in ga_wf) */
   int ga_coff[SAMPLE_WAVES][3];/* column-block index chunk offset (u16 units in image) */
   int gb_nb[GB_ROWS / 8];      /* blocks per GRU_B row block */
-  int gb_woff[GB_ROWS / 8];    /* u32 units in image [k][8] / float4 [k][8][2] in gb_wf */
+  int gb_woff[GB_ROWS / 8];    /* u32 units in image: [k][8] u32 (int8) or float4 (fp32) */
   int gb_coff[GB_ROWS / 8];    /* u16 units in image */
   int gb_rec_off;              /* byte offset of GRU_B recurrent int8 weights in image */
   /* quad int8 path (LDS image): per wave w / GRU_B row block, group of 4 slots gi:
@@ -229,9 +257,14 @@ struct SampleArgs {
   int ga_K4[SAMPLE_WAVES][3];
   int ga_qoff[SAMPLE_WAVES][3];
   int gb_qoff[GB_ROWS / 8];
-  /* matrix-core kernel: GRU_A per-lane register tables [wave][MF_LANE_U32][64
-   * lanes], 4-slot groups per wave (z/r padded to a common count, h); GRU_B
-   * A tiles [MF_GB_TILES][64] */
+  const float4 *ga_wf;   /* fp32 variant: GRU_A blocks [chunk][k][64] float4 */
+};
+
+/* The matrix-core kernels (mf_kernel, mf2_kernel; mfw_kernel reads them
+ * beside its own): GRU_A per-lane register tables [wave][MF_LANE_U32][64
+ * lanes], 4-slot groups per wave (z/r padded to a common count, h); GRU_B
+ * A tiles [MF_GB_TILES][64] */
+struct MfTables {
   const uint32_t *mf;
   const int *mf_unit;                /* [SAMPLE_WAVES * 64]: GRU_A unit of each lane */
   float mf_zr_bound;                 /* |GRU_A z/r conditioning| below this (and finite) for a workgroup's
@@ -250,50 +283,75 @@ struct SampleArgs {
   /* split models (rows longer than the own cap, mf_plan.cpp mf_plan): hosted
    * 4-slot groups after the own ones, the row each lane's hosted partial
    * sums belong to [3 gates][SAMPLE_WAVES * 64] (NA: none) */
-  int mf_split;
   int mf_nfzr[SAMPLE_WAVES];
   int mf_nfh[SAMPLE_WAVES];
   const int *mf_frow;
-  /* mfw_kernel's split form: [MFW_TAB_WAVES][MF_LANE_U32][64] tables (R
-   * waves own rows to the full caps, host waves the pieces), group counts,
-   * frow [3][SAMPLE_THREADS + 64 MFW_H_WAVES] (see mfw_split_tables) */
-  int mfw_split;
+  const uint4 *mf_gb;
+};
+
+/* mfw_kernel's split form: [MFW_TAB_WAVES][MF_LANE_U32][64] tables (R
+ * waves own rows to the full caps, host waves the pieces), group counts,
+ * frow [3][SAMPLE_THREADS + 64 MFW_H_WAVES] (see mfw_split_tables) */
+struct MfwTables {
   const uint32_t *mfw_tab;
   const int *mfw_frow;
   const int *mfw_unit;      /* [SAMPLE_THREADS]: the split form's own unit of each E / R lane */
   const float *mfw_emb[3];  /* embedding tables in the split form's lane order (as mf_emb) */
   int mfw_nzr[MFW_TAB_WAVES];
   int mfw_nh[MFW_TAB_WAVES];
-  const uint4 *mf_gb;
-  const float4 *fp_zr, *fp_h, *fp_gb; /* fp_kernel tables (see FP_ZF) */
+};
+
+/* fp_kernel (see FP_ZF) */
+struct FpTables {
+  const float4 *fp_zr, *fp_h, *fp_gb;
   const uint32_t *fp_off;
   int fp_nzr[SAMPLE_WAVES];    /* slots of the z/r chains per GRU_A wave */
   int fp_nh[SAMPLE_WAVES];     /* slots of the h chains */
-  /* fp_kernel long form (block rows beyond FP_ZF / FP_HF): every slot
-   * streamed, [wave][slot][64 lanes]: z/r packed pairs (2 float4), h float4,
-   * offsets (z quad | r quad << 8 for fpl_kz slots, then h quads) */
-  int fp_long;
+  /* long form (block rows beyond FP_ZF / FP_HF): every slot streamed,
+   * [wave][slot][64 lanes]: z/r packed pairs (2 float4), h float4, offsets
+   * (z quad | r quad << 8 for fpl_kz slots, then h quads) */
   int fpl_kz, fpl_kh;
   const float4 *fpl_zr, *fpl_h;
   const uint32_t *fpl_off;
-  const float4 *ga_wf;   /* fp32 variant: GRU_A blocks [chunk][k][64] float4 */
-  const float4 *gb_wf;   /* fp32 variant: GRU_B blocks [rb][k][8 rows][2] float4 (in c) */
-  const float *gb_recf;  /* fp32 variant: GRU_B recurrent [NB][GB_ROWS] */
-  unsigned long long *stamps; /* optional diagnostics [grid][STAMP_WAVES][16] s_memtime sums */
-  float *trace_logits;   /* optional [B][N][8] */
-  int *trace_exc;        /* optional [B][N] */
+};
+
+/* What each kernel takes: the parts side by side, members read as A.<member>,
+ * a part's helper called with A.  The order of the parts is the kernarg
+ * layout: the lockstep kernel's is the one under which it compiles closest
+ * to how it did with one struct for all kernels. */
+struct LockstepArgs : SampleModel, LockstepTables, SampleLaunch {}; /* sample_kernel */
+struct MfArgs : SampleLaunch, SampleModel, MfTables {};             /* mf_kernel, mf2_kernel */
+struct MfwArgs : SampleLaunch, SampleModel, MfTables, MfwTables {}; /* mfw_kernel */
+struct FpArgs : SampleLaunch, SampleModel, FpTables {};             /* fp_kernel */
+
+/* Which instantiation of its kernel a launcher picks: host side, read by no
+ * kernel.  The model's forms come from its load (model_host.cpp), rcp_hw
+ * from the batch's plan (kernel_choice.h SamplePlan). */
+struct SampleForm {
   int rcp_hw;            /* 1: the latency chains may use the hardware-reciprocal rcpps (equal to the
                             default Intel table only); 0: every activation through the LDS table
                             (lpcnet_batch_set_rcp_table with another host's table) */
-  int *status;           /* device view of the batch's pinned status word: a
-                            kernel that aborts sets bits (STATUS_*), the host
-                            checks after every sync */
-  int spin_limit;        /* polls before an LDS flag wait aborts (FLAG_SPIN_LIMIT_DEFAULT) */
+  int mf_split;          /* the matrix-core tables carry hosted pieces (mf_plan.cpp mf_plan) */
+  int mfw_split;         /* and mfw_kernel's split form exists (MfwTables) */
+  int fp_long;           /* fp_kernel's tables are the long form */
+};
+
+/* A loaded model's side of the sample kernels' arguments: on the host with
+ * null pointers (model_host.h HostModel), with the device pointers once
+ * uploaded (ModelArgs, the batch).  Each build step of model_host.cpp fills
+ * its family's part. */
+struct SampleTables {
+  SampleModel model;
+  LockstepTables lockstep;
+  MfTables mf;
+  MfwTables mfw;
+  FpTables fp;
+  SampleForm form;
 };
 
 constexpr int FLAG_SPIN_LIMIT_DEFAULT = 1 << 20; /* lpcnet_batch_set_spin_limit */
 constexpr int FLAG_SPIN_LIMIT_MAX = 1 << 30;     /* larger requests are clamped (int poll counters) */
-/* Status bits a sample kernel reports to the host (SampleArgs::status). */
+/* Status bits a sample kernel reports to the host (SampleLaunch::status). */
 constexpr int STATUS_FLAG_TIMEOUT = 1; /* an LDS flag wait exceeded spin_limit: output invalid */
 constexpr int STATUS_ACTIVITY = 2;     /* a multi-frame launch saw a stream become active mid-launch */
 constexpr int STATUS_SLICE_TIMEOUT = 4; /* a sliced chunk_kernel's writer waited too long for its siblings */
@@ -302,35 +360,35 @@ constexpr int STATUS_SLICE_TIMEOUT = 4; /* a sliced chunk_kernel's writer waited
  * copy when the launch has one, else the stream state. */
 #if defined(__HIP__) || defined(__HIPCC__)
 /* the same with the frame's conditioning array given (multi-frame launches) */
-__device__ __forceinline__ int frame_count_of(const SampleArgs &A, const FrameCond *cf, int sid)
+__device__ __forceinline__ int frame_count_of(const SampleLaunch &A, const FrameCond *cf, int sid)
 {
   return cf ? cf[sid].frame_count : A.st[sid].frame_count;
 }
-__device__ __forceinline__ const float *gru_a_cond_of(const FrameCond *cf, const SampleArgs &A, int sid)
+__device__ __forceinline__ const float *gru_a_cond_of(const FrameCond *cf, const SampleLaunch &A, int sid)
 {
   return cf ? cf[sid].gru_a_cond : A.st[sid].gru_a_cond;
 }
-__device__ __forceinline__ const float *gru_b_cond_of(const FrameCond *cf, const SampleArgs &A, int sid)
+__device__ __forceinline__ const float *gru_b_cond_of(const FrameCond *cf, const SampleLaunch &A, int sid)
 {
   return cf ? cf[sid].gru_b_cond : A.st[sid].gru_b_cond;
 }
-__device__ __forceinline__ const float *lpc_of(const FrameCond *cf, const SampleArgs &A, int sid)
+__device__ __forceinline__ const float *lpc_of(const FrameCond *cf, const SampleLaunch &A, int sid)
 {
   return cf ? cf[sid].lpc : A.st[sid].lpc;
 }
-__device__ __forceinline__ int frame_count_of(const SampleArgs &A, int sid)
+__device__ __forceinline__ int frame_count_of(const SampleLaunch &A, int sid)
 {
   return A.cond ? A.cond[sid].frame_count : A.st[sid].frame_count;
 }
-__device__ __forceinline__ const float *gru_a_cond_of(const SampleArgs &A, int sid)
+__device__ __forceinline__ const float *gru_a_cond_of(const SampleLaunch &A, int sid)
 {
   return A.cond ? A.cond[sid].gru_a_cond : A.st[sid].gru_a_cond;
 }
-__device__ __forceinline__ const float *gru_b_cond_of(const SampleArgs &A, int sid)
+__device__ __forceinline__ const float *gru_b_cond_of(const SampleLaunch &A, int sid)
 {
   return A.cond ? A.cond[sid].gru_b_cond : A.st[sid].gru_b_cond;
 }
-__device__ __forceinline__ const float *lpc_of(const SampleArgs &A, int sid)
+__device__ __forceinline__ const float *lpc_of(const SampleLaunch &A, int sid)
 {
   return A.cond ? A.cond[sid].lpc : A.st[sid].lpc;
 }
@@ -352,7 +410,7 @@ int frame_groups(int nstreams);        /* frame kernel workgroups (stamp rows) f
 int launch_cond_copy(const StreamState *st, FrameCond *cond, int nstreams, void *stream);
 /* dst[dmap ? dmap[k] : k] = src[smap ? smap[k] : k], k < n (device index maps) */
 int launch_state_copy(StreamState *dst, const StreamState *src, const int *dmap, const int *smap, int n, void *stream);
-int launch_sample(const SampleArgs &a, int S, int variant, int sat, int reg, int lds_bytes, void *stream);
+int launch_sample(const LockstepArgs &a, int S, int variant, int sat, int reg, int lds_bytes, void *stream);
 
 /* Frame network of up to LPC_CHUNK frames in one launch (chunk_kernel.hip):
  * f32 matrix cores, 64 (stream, frame) columns per workgroup. */
@@ -362,11 +420,11 @@ int launch_chunk(const FrameArgs &a, void *stream);
  * GRU_B products on v_mfma_i32_16x16x64_i8 in the sampler waves, two
  * workgroup barriers per sample. */
 int mf_lds_bytes(int S, int split);
-int launch_mf(const SampleArgs &a, int S, int lds_bytes, void *stream);
+int launch_mf(const MfArgs &a, const SampleForm &f, int S, int lds_bytes, void *stream);
 /* Large batches: two groups of S streams per workgroup, half a sample
  * apart (mf2_kernel.hip); no preload / trace / stamps. */
 int mf2_lds_bytes(int split);
-int launch_mf2(const SampleArgs &a, void *stream);
+int launch_mf2(const MfArgs &a, const SampleForm &f, void *stream);
 /* wide-batch kernel (mfw_kernel.hip): 2 or 3 four-stream groups per
  * 896-thread workgroup with dedicated gather/elementwise, recurrent and
  * sampler waves (split models: two groups, 1,024 threads with two host
@@ -374,338 +432,12 @@ int launch_mf2(const SampleArgs &a, void *stream);
  * stamps (-1 otherwise) */
 /* group count and selection: kernel_choice.h (mfw_groups, MFW_G3_PHASE) */
 int mfw_lds_bytes(int groups, int split = 0);
-int launch_mfw(const SampleArgs &a, int groups, void *stream);
+int launch_mfw(const MfwArgs &a, const SampleForm &f, int groups, void *stream);
 /* fp32 latency kernel: one stream per workgroup, LDS flags instead of
  * workgroup barriers (fp32 models within the FP_* limits, dense GRU_B). */
 int fp_lds_bytes();
-int launch_fp(const SampleArgs &a, void *stream);
+int launch_fp(const FpArgs &a, const SampleForm &f, void *stream);
 
-/* lpc_from_cepstrum on the device (lpc_kernel.hip).  Constant tables built
- * once per batch on the host (side_tables.cpp build_lpc_tables): the idct matrix
- * (freq.c dct_table), the 320-point kiss FFT twiddles and input permutation
- * (kiss_fft.c, lpcnet_tables.c), the band index and interpolation fraction of
- * every spectrum bin (freq.c:202-216), the compensation factors (freq.c:50). */
-constexpr int LPC_NBANDS = NBANDS;
-constexpr int LPC_WIN = 320;
-constexpr int LPC_ORDER1 = NLPC + 1;
-constexpr int LPC_CHUNK = 32;     /* frames per batched lpc_kernel launch (lpcnet_batch_synthesize_frames) */
-/* FFT input slot i (after kiss_fft's digit reversal): spectrum bin
- * k = perm[i] (mirrored to 320 - k above 160), interpolated between band
- * energies `band` and band + 1 with fraction `frac` (band = NB_BANDS - 1 for
- * the zero bin 160), imaginary part -0.f for the mirrored (conjugate) bins. */
-struct LpcSlot {
-  float frac;
-  unsigned char band, conj, pad[2];
-};
-struct LpcTables {
-  double sqrt_2_18;               /* sqrt(2./NB_BANDS) (freq.c:238) */
-  float scale;                    /* 1/320, kiss_fft's inverse scaling */
-  float dct[LPC_NBANDS * LPC_NBANDS];
-  float comp[LPC_NBANDS];
-  float twr[LPC_WIN], twi[LPC_WIN];
-  LpcSlot slot[LPC_WIN];
-};
-/* features [nstreams][NF] -> lpc_out [nstreams][NLPC] */
-/* read-only matrices an idle-time kernel touches once per 128-byte line in
- * every XCD's L2 (the deferred lpc_kernel warms the one-frame chunk
- * kernel's weights for the next tick) */
-struct L2Warm {
-  const uint32_t *m[5];
-  int lines[5];
-};
-int launch_lpc(const float *features, float *lpc_out, int nstreams, const LpcTables *tables, void *stream,
-               StreamState *ring = nullptr, int ring_depth = 0, const L2Warm *warm = nullptr);
-
-/* decode_packet (lpcnet_dec.c:81-156) on the device (decode_kernel.hip):
- * packets [npackets][nstreams][8] -> features [4 npackets][nstreams][NF],
- * each stream's vq_mem in st carried from packet to packet. */
-struct DecodeArgs {
-  const unsigned char *packets;
-  int npackets, nstreams;
-  StreamState *st;
-  const float *cb1, *cb2, *cb3; /* ceps_codebook1..3 [1024][NBANDS - 1] */
-  const float *cbd;             /* ceps_codebook_diff4 [4096][NBANDS] */
-  const float *pitch;           /* [64]: (float)(pow(2.f, m / 21.) * PITCH_MIN_PERIOD) (lpcnet_dec.c:118) */
-  float *features;
-};
-constexpr int DEC_MAX_PACKETS = LPC_CHUNK / 4; /* packets per decode launch (the frames of one chunk) */
-int launch_decode(const DecodeArgs &a, void *stream);
-
-/* The PLC prediction network (compute_plc_pred, lpcnet_plc.c:135-145) for a
- * whole batch (plc_kernel.hip): dense1 57 -> cond (tanh), two compute_gruB
- * layers cond -> n1 -> n2 (int8, DOT_PROD / USE_SU_BIAS numerics), plc_out
- * n2 -> NF (linear) and the out[19] boost.  One weight set for every stream;
- * a workgroup owns PLC_TILE streams, the N of v_mfma_i32_16x16x64_i8.
- * GRU weights as dense A tiles (the input idx expanded with zero blocks):
- * [unit tile ut][gate g][k tile kt][64 lanes] uint4, lane l = row g n + 16 ut
- * + l % 16, bytes k = 64 kt + 16 (l / 16) + 0..15 (mf_common.h mfma16).
- * seed [2][3 n] int32: rne(subias * SCALE) + 128 * rowsum(w) of the input
- * half, then of the recurrent half (x is consumed as u8 - 128). */
-constexpr int PLC_IN = 2 * NBANDS + NF + 1; /* Burg cepstrum, features, loss flag */
-constexpr int PLC_TILE = 16;                /* streams per workgroup */
-constexpr int PLC_THREADS = 512;             /* 8 waves: 256 and 1024 measured slower at 8192+ streams (profiles/r08) */
-constexpr int PLC_DIM_MAX = 512;            /* cond, n1, n2: multiples of 64 up to this */
-struct PlcArgs {
-  int nstreams;
-  int cond, n1, n2;
-  const float *in;             /* [B][PLC_IN]; null: all-zero input */
-  float *out;                  /* [B][NF]; null: discarded */
-  const unsigned char *active; /* [B]; null: every stream */
-  float *state;                /* [B][n1 + n2]: plc_gru1_state, plc_gru2_state */
-  const float *d1_w, *d1_b;    /* [PLC_IN][cond], [cond] */
-  const uint4 *g1_in, *g1_rec;
-  const int *g1_seed;
-  const uint4 *g2_in, *g2_rec;
-  const int *g2_seed;
-  const float *out_w, *out_b;  /* [n2][NF], [NF] */
-  const uint32_t *rcp;         /* RCP_ENTRIES-entry table in global memory (the table form) */
-  int rcp_hw;                  /* as SampleArgs::rcp_hw */
-};
-int plc_lds_bytes(int cond, int n1, int n2);
-int launch_plc(const PlcArgs &a, void *stream);
-
-/* The DRED RDO-VAE (dred_rdovae_enc.c:38-95, dred_rdovae_dec.c:37-98,
- * dred_rdovae.c:38-52) for a whole batch (rdovae_kernel.hip).  Encoder and
- * decoder share one stack of eight layers -- dense (tanh), GRU, dense, GRU,
- * dense, GRU, dense, dense -- whose outputs are concatenated into T floats;
- * the encoder's heads are the causal conv bits_dense (linear, latents) and
- * gdense1 -> gdense2 (tanh, the initial state), the decoder's the three state
- * layers (tanh, the GRU states from an initial state) and dec_final (linear,
- * four feature frames).  Dense weights are the blob's [in][out] floats, GRU
- * weights the PLC's A tiles and seeds (PlcArgs).  A workgroup owns PLC_TILE
- * streams. */
-constexpr int RDOVAE_DIM_MAX = 512;  /* every layer width, L, S and gdense1 */
-constexpr int RDOVAE_KSIZE_MAX = 8;  /* the conv's kernel size */
-constexpr int RDOVAE_QFRAME = 4 * NF; /* dec_final's rows */
-struct RdovaeDense {
-  const float *w, *b; /* [in][out], [out] */
-  int in, out;
-};
-struct RdovaeGru {
-  const uint4 *win, *wrec;
-  const int *seed;
-  int in, n;
-};
-struct RdovaeNet {
-  int in_dim;        /* 2 NF (encoder), L (decoder) */
-  int T, nt;         /* the concatenation; the three GRUs' units together */
-  int off[8];        /* each layer's offset in the concatenation */
-  RdovaeDense d[5];  /* stack layers 1, 3, 5, 7, 8 */
-  RdovaeGru g[3];    /* stack layers 2, 4, 6 */
-  /* encoder: bits_dense (in = ksize T), gdense1, gdense2; decoder: state1..3, dec_final */
-  RdovaeDense head[4];
-  int ksize;         /* encoder: the conv's kernel size */
-  int wmax;          /* the widest float row the kernel keeps in LDS */
-};
-struct RdovaeArgs {
-  RdovaeNet net;
-  int decoder;                 /* 0: one encoder call; 1: the decoder forms */
-  int nstreams;
-  const unsigned char *active; /* [B]; null: every stream */
-  float *state;                /* [B][nt] GRU states: the streams' own, or decode_all's scratch */
-  float *cat;                  /* [tiles][T][PLC_TILE] the concatenation, a scratch */
-  /* encoder: the input is in[s * in_stream + f * in_frame + 0..NF) of frames f = 0, 1 */
-  const float *in;
-  size_t in_stream, in_frame;
-  float *mem;                  /* [B][(ksize - 1) T] the conv's memory */
-  float *latents, *init_state; /* [B][L], [B][S] */
-  /* decoder: dec_init from d_init [B][S] when given, then nframes qframes:
-   * latent f of stream s at d_lat[(s * nframes + f) * L], its qframe at
-   * d_out[(s * nframes + f) * RDOVAE_QFRAME] */
-  const float *d_init, *d_lat;
-  float *d_out;
-  int nframes;
-  const uint32_t *rcp;
-  int rcp_hw;
-};
-int rdovae_lds_bytes(const RdovaeNet &n);
-int launch_rdovae(const RdovaeArgs &a, void *stream);
-
-/* The single-frame feature extractor (preemphasis, compute_frame_features,
- * process_single_frame: lpcnet_enc.c:872-880, 488-577, 814-870, pcount = 0)
- * for a whole batch (feat_kernel.hip).  What of LPCNetEncState crosses frames
- * on that path, per stream, outside StreamState (the synthesis snapshots keep
- * their size); all zero after a reset (lpcnet_encoder_init). */
-constexpr int NTF = 36;          /* NB_TOTAL_FEATURES */
-constexpr int PITCH_MIN = 32;    /* PITCH_MIN_PERIOD (lpcnet_private.h:14) */
-constexpr int PITCH_MAX = 256;   /* PITCH_MAX_PERIOD */
-constexpr int PITCH_STATES = PITCH_MAX - PITCH_MIN; /* Viterbi states */
-struct alignas(16) FeatState {
-  float analysis_mem[FRAME];        /* the previous frame's preemphasised input */
-  float exc[PITCH_MAX];             /* exc_buf[FRAME .. FRAME + PITCH_MAX) after the previous frame */
-  float pitch_max_path[PITCH_MAX];  /* pitch_max_path[0] */
-  float pitch_mem[NLPC];
-  float mem_preemph, pitch_filt, pitch_max_path_all;
-  int best_i;                       /* in [0, PITCH_STATES) */
-};
-/* host-built constants: half_window (dump_lpcnet_tables.c:83-84) and, per
- * spectrum bin below 160, (float)j/band_size (freq.c:141) */
-struct FeatTables {
-  float half_window[FRAME];
-  float frac[FRAME];
-  int band_start[NBANDS]; /* eband5ms[b] * WINDOW_SIZE_5MS (freq.c:45-48, 138) */
-  int pad[2];
-};
-struct FeatArgs {
-  int nstreams;
-  const short *pcm;            /* [B][FRAME], or */
-  const float *pcm_f;          /* [B][FRAME] when pcm is null */
-  float *features;             /* stream s writes features[s * stride .. + row) */
-  int row;                     /* NF or NTF */
-  int stride;                  /* floats between two streams' rows, >= row (row: a dense [B][row]) */
-  const unsigned char *active; /* [B]; null: every stream */
-  FeatState *state;            /* [B] */
-  const LpcTables *lpc_tab;
-  const FeatTables *tab;
-  /* the superframe form only (launch_feat_super): frame k of 4; features is
-   * then [B][NF] (row = NF) of that frame */
-  int k;
-  float *xc_out;               /* [B][8][PITCH_MAX]: rows 2 k, 2 k + 1 written */
-  float *fw_out;               /* [B][8] */
-  float *lpc_out;              /* [B][NLPC] of frame k */
-};
-int launch_feat(const FeatArgs &a, void *stream);
-int launch_feat_super(const FeatArgs &a, void *stream);
-
-/* burg_cepstral_analysis (freq.c:156-199, burg.c:98-245) for a whole batch
- * (burg_kernel.hip): 160 samples per stream -> 18 sums and 18 differences of
- * the two half-frames' Burg cepstra.  No state, no weights.  The table is a
- * struct of its own, uploaded on first use, in no digest. */
-constexpr int BURG_N = 2 * NBANDS;          /* floats per stream */
-constexpr int BURG_LEN = FRAME / 2 - 1;     /* burg_in samples of a half-frame (len - 1) */
-constexpr int BURG_NC = NLPC + 2;           /* C0, lags 1..16, the energy of the first 16 samples */
-struct BurgTables {
-  double pw[NLPC]; /* pow(.995, i + 1) (freq.c:174), the host's */
-};
-constexpr int BURG_FILL_ZERO = 1; /* +0.f into out[BURG_N .. BURG_N + NF) */
-constexpr int BURG_FILL_FLAG = 2; /* flag into out[PLC_IN - 1] */
-struct BurgArgs {
-  int nstreams;
-  const short *pcm;            /* [B][FRAME], or */
-  const float *pcm_f;          /* [B][FRAME] when pcm is null */
-  float *out;                  /* stream s writes out[s * stride .. + BURG_N) */
-  int stride;                  /* >= BURG_N; >= PLC_IN with a fill */
-  int fill;                    /* BURG_FILL_*: the rest of a predictor input row that starts at out */
-  float flag;
-  const unsigned char *active; /* [B]; null: every stream */
-  const LpcTables *lpc_tab;
-  const FeatTables *tab;
-  const BurgTables *btab;
-  /* scratch of one call, column 2 s + h of 2 B: the autocorrelations, the
-   * recursion's 32 samples, then the filter input and the gain */
-  double *cbuf;                /* [BURG_NC][2 B] */
-  float *xbuf;                 /* [2 NLPC][2 B] */
-  float *obuf;                 /* [NLPC + 1][2 B] */
-};
-int launch_burg(const BurgArgs &a, void *stream);
-/* a predictor input row without its Burg part: +0.f into rows[s][0 .. BURG_N),
- * flag into rows[s][PLC_IN - 1] of every live stream; rows [B][PLC_IN] */
-int launch_plc_row_fill(float *rows, float flag, const unsigned char *active, int nstreams, void *stream);
-
-/* lpcnet_encode / lpcnet_compute_features after their four frame analyses:
- * process_superframe (lpcnet_enc.c:579-743) for a whole batch (enc_kernel.hip).
- * The scratch below is written and consumed within one packet of one call and
- * is no state; what crosses packets is FeatState (the Viterbi rows are the
- * single-frame path's) and each stream's encoder vq_mem.
- * Distances of 1e15f or more, and NaN, are outside the contract: the
- * reference then reads uninitialised indices (lpcnet_enc.c:53-78, 138-147);
- * here every index stays inside its codebook, and its value is unspecified.
- * PCM input cannot produce such distances. */
-constexpr int ENC_PITCH_THR = 63; /* main_pitch = how many of these center_pitch reaches */
-struct EncTables {
-  float pitch_thr[ENC_PITCH_THR + 1]; /* ascending; [63] pads */
-};
-struct EncArgs {
-  int nstreams;
-  int quantize;                /* 1: lpcnet_encode (quantize = encode = 1); 0: lpcnet_compute_features */
-  const unsigned char *active; /* [B]; null: every stream */
-  FeatState *state;            /* [B] */
-  float *vq_mem;               /* [B][NBANDS], the encoder's (not the decoder's) */
-  float *xc;                   /* [B][8][PITCH_MAX] scratch: xc[2..9] */
-  float *fw;                   /* [B][8] scratch: frame_weight[2..9] */
-  float *feat;                 /* [4][B][NF] scratch: cepstra in, st->features[k][0..19] out */
-  int *fields;                 /* [B][4] scratch: c0_id + 64, main_pitch, modulation field, corr_id */
-  const float *lpc;            /* [4][B][NLPC] scratch (enc_out_kernel) */
-  const EncTables *tab;
-  const float *cb1, *cb2, *cb3, *cbd, *pitch; /* as DecodeArgs */
-  unsigned char *packets;      /* [B][8]; null: not written */
-  float *features;             /* [4][B][row]; null: not written */
-  int row;                     /* NF or NTF */
-};
-/* the Viterbi pass over xc[2..9], backtrack, pitch regression and quantisation, c0 */
-int launch_enc_pitch(const EncArgs &a, void *stream);
-/* quantize_3stage_mbest, quantize_diff, double_interp_search,
- * perform_double_interp and bits_pack (quantize = 1 only) */
-int launch_enc_vq(const EncArgs &a, void *stream);
-/* live streams' rows of feat | lpc into features */
-int launch_enc_out(const EncArgs &a, void *stream);
-/* main_pitch of lpcnet_enc.c:678-679 from the threshold table, host and device alike */
-__host__ __device__ inline int enc_main_pitch(const float *thr, float cp)
-{
-  int m = 0;
-  if (cp < __builtin_inff()) /* inf: log = inf, floor, (int) = INT_MIN, IMIN, IMAX -> 0; NaN compares false */
-    for (int i = 0; i < ENC_PITCH_THR; i++) m += cp >= thr[i];
-  return m;
-}
-
-/* The data side of lpcnet_plc_update / lpcnet_plc_conceal between their
- * network and analysis calls (conceal_kernel.hip): per stream, beside
- * StreamState (the synthesis snapshots keep their size), what of
- * LPCNetPLCState (lpcnet_private.h:78-106) the causal modes carry, and the
- * scratch a tick hands over through.  Every launcher takes the streams it
- * works on as an index list idx [n] in device memory; a stream appears in a
- * list at most once. */
-constexpr int CONCEAL_FEC_ROWS = 100; /* PLC_MAX_FEC */
-constexpr int CONCEAL_DEFER = 4;      /* MAX_FEATURE_BUFFER_SIZE */
-struct ConcealData {
-  int nstreams;
-  int delay;          /* FEATURES_DELAY the buffers were laid out for */
-  int buf;            /* PLC_BUF_SIZE = delay * FRAME + FRAME / 2 */
-  int nt;             /* n1 + n2 floats of one PLCNetState */
-  float *features;    /* [B][NF] st->features */
-  short *pcm;         /* [B][buf + FRAME] st->pcm */
-  double *dc;         /* [B][2] dc_mem, syn_dc */
-  float *copy;        /* [B][delay + 1][nt] plc_copy */
-  float *fec;         /* [B][CONCEAL_FEC_ROWS][NF] */
-  float *defer;       /* [B][CONCEAL_DEFER][NF] the LPCNetState's feature_buffer */
-  float *plc_state;   /* [B][nt] plc_net (the predictor's own state) */
-  /* scratch of one tick */
-  float *rows;        /* [B][PLC_IN] the predictor's input row */
-  short *lp;          /* [B][FRAME] lpcnet_plc_update_causal's lp */
-  int *delta;         /* [B] its delta; zero without the DC filter */
-  short *tmp;         /* [B][FRAME / 2] the speculative half frame */
-  const float *blend_w; /* [FRAME / 2] (float)(.5 - .5*cos(M_PI*i/80)), the host's cos */
-};
-enum { CONCEAL_DC_REMOVE = 0, CONCEAL_DC_RESTORE = 1, CONCEAL_DC_CONCEAL = 2 };
-/* the DC filter on io [B][FRAME] (lpcnet_plc.c:195-204, 283-287, 330-335): one lane per stream */
-int launch_conceal_dc(const ConcealData &d, const int *idx, int n, short *io, int mode, void *stream);
-/* io[0 .. 80) = blend of io and tmp - delta (:225-229) */
-int launch_conceal_blend(const ConcealData &d, const int *idx, int n, short *io, void *stream);
-/* features[0] = MAX16(-10, features[0] + att_table[.]) (:318-319) */
-int launch_conceal_attenuate(const ConcealData &d, const int *idx, int n, int loss_count, void *stream);
-/* st->pcm[dst_off .. + cnt) = (src_buf ? st->pcm : io row)[src_off .. + cnt); the ranges may overlap */
-int launch_conceal_move(const ConcealData &d, const int *idx, int n, const short *io, int dst_off, int src_buf, int src_off, int cnt,
-                        void *stream);
-/* plc_copy ring push (:305-306); plc_net = plc_copy[k] */
-int launch_conceal_plc_push(const ConcealData &d, const int *idx, int n, void *stream);
-int launch_conceal_plc_restore(const ConcealData &d, const int *idx, int n, int k, void *stream);
-/* fec[pos] into features and into the row's columns 36..55, flag -1, zeros before (:149-157) */
-int launch_conceal_fec_fetch(const ConcealData &d, const int *idx, int n, int pos, void *stream);
-/* run_frame_network_deferred's buffer push: analysed ? rows[36 .. 56) : features, `fill` frames held before */
-int launch_conceal_defer_push(const ConcealData &d, const int *idx, int n, int analysed, int fill, void *stream);
-/* work order [n][NF] / [n][N] from the streams' rows: w_feat (null: none) from
- * features (defer_row < 0) or the deferred buffer's row; w_pcm (null: none)
- * from st->pcm (src_buf) or the io row, at src_off */
-int launch_conceal_gather(const ConcealData &d, const int *idx, int n, float *w_feat, int defer_row, short *w_pcm, const short *io,
-                          int src_buf, int src_off, int N, void *stream);
-/* w_pcm [n][N] to the io rows at dst_off, or to tmp (io null) */
-int launch_conceal_scatter(const ConcealData &d, const int *idx, int n, const short *w_pcm, short *io, int dst_off, int N,
-                           void *stream);
-/* lpcnet_reset_signal (lpcnet.c:226-233) on st[idx[k]]; ulaw0 = lin2ulaw(0.f) */
-int launch_conceal_reset_signal(StreamState *st, const int *idx, int n, int ulaw0, void *stream);
-/* lpcnet_plc_fec_add's RNN_MOVE (:121) and RNN_COPY (:126) on one stream */
-int launch_conceal_fec_compact(const ConcealData &d, int s, int from, int rows, void *stream);
-int launch_conceal_fec_store(const ConcealData &d, int s, int pos, const float *features /* host, [NF] */, void *stream);
 
 }  // namespace lpcnet_mi355x
 

@@ -21,7 +21,7 @@
  * GRU_A register tables and GRU_B tiles serve 2S streams.  Used for batches
  * of >= 2048 streams (a launch still fills every CU); preload, trace and
  * stamps take mf_kernel.  Samples t run over all frames of a
- * multi-frame launch (SampleArgs::nframes); the samplers write each output
+ * multi-frame launch (SampleLaunch::nframes); the samplers write each output
  * sample straight to global memory.
  */
 #include <hip/hip_runtime.h>
@@ -63,7 +63,7 @@ int mf2_lds_bytes(int split)
  * LDS: one buffer per group, added into by the group's recurrent product and
  * merged (then cleared) by its next elementwise step, a barrier apart */
 template <int S, bool SPLIT, bool HWR>
-__global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
+__global__ __launch_bounds__(MF_THREADS) void mf2_kernel(MfArgs A)
 {
   static_assert(S == 4, "mf2_kernel: four streams per group (a sampler wave carries two, one per half)");
   extern __shared__ uint4 lds4[];
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
     /* group g's inputs of a frame: its conditioning (lane-private LDS
      * entries) and this wave's range word */
     auto stage = [&](int g, const FrameCond *cf, int par) {
-      const bool in_range = ga_stage_cond<S>(A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
+      const bool in_range = ga_stage_cond<S>(A, A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
       const bool wave_ok = __ballot(!in_range) == 0ull; /* every lane active: not inside the lane-0 branch */
       if (lane == 0) okw[(par * 2 + g) * 8 + wv] = wave_ok;
     };
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
     auto stage_frame = [&](int g, const FrameCond *cf) {
       for (int e = lane; e < S * GB_ROWS; e += 64) {
         const int s = e / GB_ROWS, r = e % GB_ROWS;
-        myg[g * S * GB_ROWS + e] = gb_in_seed(A, cf, min(s0 + g * S + s, A.nstreams - 1), r);
+        myg[g * S * GB_ROWS + e] = gb_in_seed(A, A, cf, min(s0 + g * S + s, A.nstreams - 1), r);
       }
       if (samp_w && hl < NLPC) lpcb[(g * S + ms) * NLPC + hl] = lpc_of(cf, A, min(s0 + g * S + ms, A.nstreams - 1))[hl];
     };
@@ -512,7 +512,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf2_kernel(SampleArgs A)
 }
 
 template <int S, bool SPLIT, bool HWR>
-static int launch_mf2_t(const SampleArgs &a, hipStream_t stream)
+static int launch_mf2_t(const MfArgs &a, hipStream_t stream)
 {
   if (ensure_dyn_lds((const void *)mf2_kernel<S, SPLIT, HWR>, 160 * 1024 - IMG_VAR)) return -1;
   const int grid = (a.nstreams + 2 * S - 1) / (2 * S);
@@ -521,15 +521,15 @@ static int launch_mf2_t(const SampleArgs &a, hipStream_t stream)
 }
 
 template <bool HWR>
-static int launch_mf2_h(const SampleArgs &a, hipStream_t st)
+static int launch_mf2_h(const MfArgs &a, const SampleForm &f, hipStream_t st)
 {
-  return a.mf_split ? launch_mf2_t<4, true, HWR>(a, st) : launch_mf2_t<4, false, HWR>(a, st);
+  return f.mf_split ? launch_mf2_t<4, true, HWR>(a, st) : launch_mf2_t<4, false, HWR>(a, st);
 }
 
-int launch_mf2(const SampleArgs &a, void *stream)
+int launch_mf2(const MfArgs &a, const SampleForm &f, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
-  return a.rcp_hw ? launch_mf2_h<true>(a, st) : launch_mf2_h<false>(a, st);
+  return f.rcp_hw ? launch_mf2_h<true>(a, f, st) : launch_mf2_h<false>(a, f, st);
 }
 
 }  // namespace lpcnet_mi355x

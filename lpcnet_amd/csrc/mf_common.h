@@ -530,11 +530,11 @@ __device__ __forceinline__ v4i mfma16(const v4i &w, const v4i &x, v4i acc)
  * group's first stream), into LDS by lane position: cg[gate][tid][stream]
  * (conflict-free reads, from the unit's column; read by this thread only).
  * Returns whether the states and the conditioning are within the host's
- * range bounds (SampleArgs::mf_zr_bound); NaN fails every compare: such a
+ * range bounds (MfTables::mf_zr_bound); NaN fails every compare: such a
  * workgroup takes the exact path.  The caller ballots it into its range
  * word. */
 template <int S>
-__device__ __forceinline__ bool ga_stage_cond(const SampleArgs &A, const FrameCond *cf, int sg, int i, int tid,
+__device__ __forceinline__ bool ga_stage_cond(const SampleLaunch &A, const MfTables &T, const FrameCond *cf, int sg, int i, int tid,
                                               const float (&st)[S], float *cg)
 {
   bool in_range = true;
@@ -546,8 +546,8 @@ __device__ __forceinline__ bool ga_stage_cond(const SampleArgs &A, const FrameCo
     cg[tid * S + s] = cz;
     cg[(NA + tid) * S + s] = cr;
     cg[(2 * NA + tid) * S + s] = ch;
-    in_range &= fabsf(st[s]) <= 2.f && fabsf(cz) <= A.mf_zr_bound && fabsf(cr) <= A.mf_zr_bound &&
-                fabsf(ch) <= A.mf_h_bound;
+    in_range &= fabsf(st[s]) <= 2.f && fabsf(cz) <= T.mf_zr_bound && fabsf(cr) <= T.mf_zr_bound &&
+                fabsf(ch) <= T.mf_h_bound;
   }
   return in_range;
 }
@@ -567,20 +567,20 @@ __device__ __forceinline__ uint32_t mf_frow_pack(const int *frow, int tid, int s
 /* GRU_B accumulator seeds (nnet.c:347-356 with the offset-128 correction:
  * cvt_rne((bias + cond) * SCALE) + 128 rowsum(w)): row r of the input
  * product for stream sid in a frame, and of the recurrent product */
-__device__ __forceinline__ int gb_in_seed(const SampleArgs &A, const FrameCond *cf, int sid, int r)
+__device__ __forceinline__ int gb_in_seed(const SampleLaunch &A, const SampleModel &M, const FrameCond *cf, int sid, int r)
 {
-  return cvt_rne((A.gb_par[r] + gru_b_cond_of(cf, A, sid)[r]) * kScale) + A.gb_wsum[r];
+  return cvt_rne((M.gb_par[r] + gru_b_cond_of(cf, A, sid)[r]) * kScale) + M.gb_wsum[r];
 }
 
-__device__ __forceinline__ int gb_rec_seed(const SampleArgs &A, int r)
+__device__ __forceinline__ int gb_rec_seed(const SampleModel &M, int r)
 {
-  return cvt_rne(A.gb_par[GB_ROWS + r] * kScale) + A.gb_wsum[GB_ROWS + r];
+  return cvt_rne(M.gb_par[GB_ROWS + r] * kScale) + M.gb_wsum[GB_ROWS + r];
 }
 
 /* entry e = tile * 64 + lane of the GRU_B weight tiles (input 18, recurrent 3) */
-__device__ __forceinline__ v4i gb_tile(const SampleArgs &A, int e)
+__device__ __forceinline__ v4i gb_tile(const MfTables &T, int e)
 {
-  const uint4 u = A.mf_gb[e];
+  const uint4 u = T.mf_gb[e];
   return v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
 }
 

@@ -2,7 +2,7 @@
  * mf_kernel.hip -- the matrix-core sample kernel: lpcnet_synthesize_tail_impl
  * (lpcnet.c:235-271) for S <= 4 streams per 512-thread workgroup, persistent
  * over the N samples of one frame, or of several frames in one launch
- * (SampleArgs::nframes: no ~10 us dispatch gap and prologue per frame).
+ * (SampleLaunch::nframes: no ~10 us dispatch gap and prologue per frame).
  * Default for non-saturating int8 models.
  *
  * Both int8 products run on the matrix cores, from register-resident weights,
@@ -65,10 +65,10 @@ int mf_lds_bytes(int S, int split)
 }
 
 /* DIAG: 0 the production kernel, 1 with the per-sample logit / excitation
- * trace (SampleArgs::trace_logits), 2 with the s_memtime phase stamps
- * (SampleArgs::stamps): the plain kernel carries no diagnostic branch */
+ * trace (SampleLaunch::trace_logits), 2 with the s_memtime phase stamps
+ * (SampleLaunch::stamps): the plain kernel carries no diagnostic branch */
 template <int S, int DIAG, bool SPLIT, bool HWR>
-__global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
+__global__ __launch_bounds__(MF_THREADS) void mf_kernel(MfArgs A)
 {
   constexpr bool TRACE = DIAG == 1;
   extern __shared__ uint4 lds4[];
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
         pcm_out += (size_t)A.nstreams * A.N;
       }
       /* every input of this frame within the host's range bounds
-       * (SampleArgs::mf_zr_bound, and mf_h_bound: the h gate's tanh input
+       * (MfTables::mf_zr_bound, and mf_h_bound: the h gate's tanh input
        * below kTanhFinBound): the elementwise step's range selects are
        * dead, take the select-free forms (uniform per workgroup) */
       fast = true;
@@ -803,7 +803,7 @@ __global__ __launch_bounds__(MF_THREADS) void mf_kernel(SampleArgs A)
 }
 
 template <int S, int DIAG, bool SPLIT, bool HWR = true>
-static int launch_mf_t(const SampleArgs &a, int lds_bytes, hipStream_t stream)
+static int launch_mf_t(const MfArgs &a, int lds_bytes, hipStream_t stream)
 {
   if (ensure_dyn_lds((const void *)mf_kernel<S, DIAG, SPLIT, HWR>, 160 * 1024 - IMG_VAR)) return -1;
   const int grid = warm_grid((a.nstreams + S - 1) / S, a.nstreams);
@@ -813,17 +813,17 @@ static int launch_mf_t(const SampleArgs &a, int lds_bytes, hipStream_t stream)
 }
 
 template <int S>
-static int launch_mf_s(const SampleArgs &a, int lds_bytes, hipStream_t st)
+static int launch_mf_s(const MfArgs &a, const SampleForm &f, int lds_bytes, hipStream_t st)
 {
-  if (!a.rcp_hw) {
+  if (!f.rcp_hw) {
     /* another host's rcpps table: every activation through it (production
      * and trace forms; no stamped build) */
     if (a.stamps) return -1;
-    if (a.mf_split)
+    if (f.mf_split)
       return a.trace_logits ? launch_mf_t<S, 1, true, false>(a, lds_bytes, st) : launch_mf_t<S, 0, true, false>(a, lds_bytes, st);
     return a.trace_logits ? launch_mf_t<S, 1, false, false>(a, lds_bytes, st) : launch_mf_t<S, 0, false, false>(a, lds_bytes, st);
   }
-  if (a.mf_split)
+  if (f.mf_split)
     return a.trace_logits ? launch_mf_t<S, 1, true>(a, lds_bytes, st)
            : a.stamps     ? launch_mf_t<S, 2, true>(a, lds_bytes, st)
                           : launch_mf_t<S, 0, true>(a, lds_bytes, st);
@@ -833,12 +833,12 @@ static int launch_mf_s(const SampleArgs &a, int lds_bytes, hipStream_t st)
                         : launch_mf_t<S, 0, false>(a, lds_bytes, st);
 }
 
-int launch_mf(const SampleArgs &a, int S, int lds_bytes, void *stream)
+int launch_mf(const MfArgs &a, const SampleForm &f, int S, int lds_bytes, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
-  if (S == 4) return launch_mf_s<4>(a, lds_bytes, st);
-  if (S == 2) return launch_mf_s<2>(a, lds_bytes, st);
-  return launch_mf_s<1>(a, lds_bytes, st);
+  if (S == 4) return launch_mf_s<4>(a, f, lds_bytes, st);
+  if (S == 2) return launch_mf_s<2>(a, f, lds_bytes, st);
+  return launch_mf_s<1>(a, f, lds_bytes, st);
 }
 
 }  // namespace lpcnet_mi355x

@@ -266,7 +266,7 @@ __device__ __forceinline__ void mfw_zr(const unsigned char *xg, const uint32_t (
  * unit's row, accumulated from 0, its int32 partial sums added into that
  * row's part words (prt) instead of stored to trm */
 template <int MFW_G, int Z, int H, bool SPLIT = false, bool HOST = false>
-__device__ __forceinline__ void mfw_r_role(const SampleArgs &A, unsigned char *xa, int *trm, int r, int lane, int total,
+__device__ __forceinline__ void mfw_r_role(const MfwArgs &A, unsigned char *xa, int *trm, int r, int lane, int total,
                                            int *prt = nullptr)
 {
   /* this lane's weight words and packed column quads (mf_plan.cpp mf tables:
@@ -368,7 +368,7 @@ __device__ __forceinline__ void mfw_r_role(const SampleArgs &A, unsigned char *x
 }
 
 template <bool HWR, int MFW_G, bool SPLIT = false>
-__global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_kernel(SampleArgs A)
+__global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_kernel(MfwArgs A)
 {
   /* the rcpps table in LDS for the E waves: two groups, unsplit, the
    * device table (TAB); the split form, its 2,048-entry form beside the part
@@ -506,7 +506,7 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
     /* group g's inputs of a frame: its conditioning (lane-private LDS
      * entries) and this wave's range word */
     auto stage = [&](int g, const FrameCond *cf, int par) {
-      const bool in_range = ga_stage_cond<S>(A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
+      const bool in_range = ga_stage_cond<S>(A, A, cf, s0 + g * S, i, tid, st[g], cnd + g * GA_ROWS * S);
       const bool wave_ok = __ballot(!in_range) == 0ull; /* every lane active: not inside the lane-0 branch */
       if (lane == 0) okw[(par * MFW_G + g) * 8 + wv] = wave_ok;
     };
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
     for (int e = lane; e < S * GB_ROWS; e += 64) {
       const int s = e / GB_ROWS, rr = e % GB_ROWS;
       if ((s >> 1) != sw) continue;
-      gbs[g * S * GB_ROWS + e] = gb_in_seed(A, cf, min(s0 + g * S + s, A.nstreams - 1), rr);
+      gbs[g * S * GB_ROWS + e] = gb_in_seed(A, A, cf, min(s0 + g * S + s, A.nstreams - 1), rr);
     }
     if (hl < NLPC) lpcb[(g * S + ms) * NLPC + hl] = lpc_of(cf, A, min(s0 + g * S + ms, A.nstreams - 1))[hl];
   };
@@ -878,7 +878,7 @@ __global__ __launch_bounds__(SPLIT ? MFW_THREADS_SPLIT : MFW_THREADS) void mfw_k
 }
 
 template <int G, bool SPLIT = false>
-static int launch_mfw_g(const SampleArgs &a, void *stream)
+static int launch_mfw_g(const MfwArgs &a, void *stream)
 {
   using L = MfwLds<G>;
   const int bytes = L::total + (SPLIT ? MFW_PRT : 0);
@@ -889,12 +889,12 @@ static int launch_mfw_g(const SampleArgs &a, void *stream)
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_mfw(const SampleArgs &a, int groups, void *stream)
+int launch_mfw(const MfwArgs &a, const SampleForm &f, int groups, void *stream)
 {
-  if (!a.rcp_hw || a.preload || a.trace_logits || a.stamps) return -1;
-  if (a.mf_split) {
+  if (!f.rcp_hw || a.preload || a.trace_logits || a.stamps) return -1;
+  if (f.mf_split) {
     /* split models: the host-wave form, two groups, where its tables exist */
-    if (!a.mfw_split || groups != 2) return -1;
+    if (!f.mfw_split || groups != 2) return -1;
     return launch_mfw_g<2, true>(a, stream);
   }
   if (groups == 2) return launch_mfw_g<2>(a, stream);

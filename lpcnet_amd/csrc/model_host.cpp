@@ -417,14 +417,14 @@ void lockstep_row_lengths(const Blob &B, int gaK[SAMPLE_WAVES][3])
 /* quad layout: wave w, gate g, group gi of 4 slots, lane l = 8*(row block in wave) + row.
  * The z, r and h groups of one wave are contiguous (weights and column
  * words alike), so the kernel runs them as one software-pipelined stream. */
-void build_quad_layout(const Blob &B, const int gaK[SAMPLE_WAVES][3], Image &I, SampleArgs &sa)
+void build_quad_layout(const Blob &B, const int gaK[SAMPLE_WAVES][3], Image &I, LockstepTables &lt)
 {
   const std::vector<std::vector<int>> &ga_blocks = B.ga.blocks, &gb_blocks = B.gb_blocks;
   for (int w = 0; w < SAMPLE_WAVES; w++) {
     int K4[3], G = 0;
     for (int g = 0; g < 3; g++) {
       K4[g] = (gaK[w][g] + 3) / 4;
-      sa.ga_K4[w][g] = K4[g];
+      lt.ga_K4[w][g] = K4[g];
       G += K4[g];
     }
     std::vector<uint32_t> q((size_t)std::max(G, 1) * 64 * 4, 0), c((size_t)std::max(G, 1) * 8, 0);
@@ -442,8 +442,8 @@ void build_quad_layout(const Blob &B, const int gaK[SAMPLE_WAVES][3], Image &I, 
     const int qbase = (int)(I.put(q.data(), q.size() * 4) / 16);
     const int cbase = (int)(I.put(c.data(), c.size() * 4) / 4);
     for (int g = 0, acc = 0; g < 3; acc += K4[g], g++) {
-      sa.ga_qoff[w][g] = qbase + acc * 64;
-      sa.ga_coff[w][g] = cbase + acc * 8;
+      lt.ga_qoff[w][g] = qbase + acc * 64;
+      lt.ga_coff[w][g] = cbase + acc * 8;
     }
   }
   for (int rb = 0; rb < GB_ROWS / 8; rb++) {
@@ -457,8 +457,36 @@ void build_quad_layout(const Blob &B, const int gaK[SAMPLE_WAVES][3], Image &I, 
         if (r == 0) c[(j / 4) * 8 + ks] |= (uint32_t)(gb_blocks[rb][k] / 4) << (8 * (j & 3));
       }
     }
-    sa.gb_qoff[rb] = (int)(I.put(q.data(), q.size() * 4) / 16);
-    sa.gb_coff[rb] = (int)(I.put(c.data(), c.size() * 4) / 4);
+    lt.gb_qoff[rb] = (int)(I.put(q.data(), q.size() * 4) / 16);
+    lt.gb_coff[rb] = (int)(I.put(c.data(), c.size() * 4) / 4);
+  }
+}
+
+/* The dual-FC walk's form for the matrix-core kernel (MfTables::fc_fin). */
+void build_fc_bound(const Blob &B, const LoadEnv &env, HostModel &H)
+{
+  MfTables &mt = H.sample.mf;
+  /* dual-FC node sums (nnet.c:193-199) are bounded by |bias| + 2 sum|w|
+   * for GRU_B states within [-2, 2]: while that is finite and below
+   * kTanhFinBound (2^30; every partial sum of the kernel's float chain is
+   * bounded by it too), tanh8's flush and NaN selects are dead
+   * (tanh_x86_fin_n).  Node 0 is never walked (nnet.c:190: i = (1 << b) | val)
+   * but is bounded like the rest. */
+  bool fin = true;
+  double worst = 0;
+  for (int c = 0; c < 2; c++)
+    for (int i = 0; i < 256; i++) {
+      double bd = fabs((double)B.fc_b[c * 256 + i]);
+      for (int j = 0; j < 16; j++) bd += 2.0 * fabs((double)B.fc_w[i * 32 + c * 16 + j]);
+      fin = fin && std::isfinite(bd) && bd < (double)kTanhFinBound;
+      worst = std::isfinite(bd) ? std::max(worst, bd) : INFINITY;
+    }
+  mt.fc_fin = fin && !env.fc_exact ? 1 : 0;
+  if (env.verbose) {
+    char line[160];
+    snprintf(line, sizeof line, "lpcnet: dual-FC walk: %s form (largest node bound %g, limit %g%s)\n",
+             mt.fc_fin ? "select-free" : "exact", worst, (double)kTanhFinBound, env.fc_exact ? ", exact forced" : "");
+    H.bounds_note += line;
   }
 }
 
@@ -469,7 +497,7 @@ void build_lockstep_image(const Blob &B, const LoadEnv &env, HostModel &H)
 {
   const bool int8 = B.int8;
   const std::vector<std::vector<int>> &ga_blocks = B.ga.blocks, &gb_blocks = B.gb_blocks;
-  SampleArgs &sa = H.sa;
+  LockstepTables &lt = H.sample.lockstep;
   std::vector<unsigned char> &img = H.img;
   img.assign(IMG_VAR, 0);
   memcpy(&img[IMG_RCP], H.rcp_dev.data(), RCP_ENTRIES * 4);
@@ -482,34 +510,10 @@ void build_lockstep_image(const Blob &B, const LoadEnv &env, HostModel &H)
     memcpy(&img[IMG_LOGIT + 4 * i], &lg, 4);
   }
   memcpy(&img[IMG_FCW], B.fc_w, 256 * 32 * 4);
-  {
-    /* dual-FC node sums (nnet.c:193-199) are bounded by |bias| + 2 sum|w|
-     * for GRU_B states within [-2, 2]: while that is finite and below
-     * kTanhFinBound (2^30; every partial sum of the kernel's float chain is
-     * bounded by it too), tanh8's flush and NaN selects are dead
-     * (tanh_x86_fin_n).  Node 0 is never walked (nnet.c:190: i = (1 << b) | val)
-     * but is bounded like the rest. */
-    bool fin = true;
-    double worst = 0;
-    for (int c = 0; c < 2; c++)
-      for (int i = 0; i < 256; i++) {
-        double bd = fabs((double)B.fc_b[c * 256 + i]);
-        for (int j = 0; j < 16; j++) bd += 2.0 * fabs((double)B.fc_w[i * 32 + c * 16 + j]);
-        fin = fin && std::isfinite(bd) && bd < (double)kTanhFinBound;
-        worst = std::isfinite(bd) ? std::max(worst, bd) : INFINITY;
-      }
-    sa.fc_fin = fin && !env.fc_exact ? 1 : 0;
-    if (env.verbose) {
-      char line[160];
-      snprintf(line, sizeof line, "lpcnet: dual-FC walk: %s form (largest node bound %g, limit %g%s)\n",
-               sa.fc_fin ? "select-free" : "exact", worst, (double)kTanhFinBound, env.fc_exact ? ", exact forced" : "");
-      H.bounds_note += line;
-    }
-  }
   memcpy(&img[IMG_FCB], B.fc_b, 512 * 4);
   memcpy(&img[IMG_FCF], B.fc_f, 512 * 4);
   Image I{img};
-  if (int8) sa.gb_rec_off = (int)I.put(H.gbrec, 3 * NB * NB);
+  if (int8) lt.gb_rec_off = (int)I.put(H.gbrec, 3 * NB * NB);
   int gaK[SAMPLE_WAVES][3];
   lockstep_row_lengths(B, gaK);
   bool reg = int8;
@@ -520,28 +524,28 @@ void build_lockstep_image(const Blob &B, const LoadEnv &env, HostModel &H)
     if ((int)gb_blocks[rb].size() > 8 * REG_GB) reg = false;
   if (env.no_quad) reg = false;
   H.reg = reg;
-  if (reg) build_quad_layout(B, gaK, I, sa);
+  if (reg) build_quad_layout(B, gaK, I, lt);
   /* GRU_B input blocks: [rb][k][row] (u32 int8 row quads | float4 fp32 rows) */
   for (int rb = 0; rb < GB_ROWS / 8; rb++) {
     int nb = (int)gb_blocks[rb].size();
-    sa.gb_nb[rb] = nb;
+    lt.gb_nb[rb] = nb;
     if (reg) continue;
     if (int8) {
       std::vector<uint32_t> w(nb * 8);
       for (int k = 0; k < nb; k++)
         for (int r = 0; r < 8; r++) memcpy(&w[k * 8 + r], (const int8_t *)B.gbw + 32 * (B.gb_first[rb] + k) + 4 * r, 4);
-      sa.gb_woff[rb] = (int)(I.put(w.data(), w.size() * 4) / 4);
+      lt.gb_woff[rb] = (int)(I.put(w.data(), w.size() * 4) / 4);
     } else {
       std::vector<float> w(nb * 8 * 4);
       const float *src = (const float *)B.gbw;
       for (int k = 0; k < nb; k++)
         for (int r = 0; r < 8; r++)
           for (int c = 0; c < 4; c++) w[(k * 8 + r) * 4 + c] = src[32 * (B.gb_first[rb] + k) + c * 8 + r];
-      sa.gb_woff[rb] = (int)(I.put(w.data(), w.size() * 4) / 4);
+      lt.gb_woff[rb] = (int)(I.put(w.data(), w.size() * 4) / 4);
     }
     std::vector<uint16_t> cbs(nb);
     for (int k = 0; k < nb; k++) cbs[k] = (uint16_t)(gb_blocks[rb][k] / 4);
-    sa.gb_coff[rb] = (int)(I.put(cbs.data(), cbs.size() * 2) / 2);
+    lt.gb_coff[rb] = (int)(I.put(cbs.data(), cbs.size() * 2) / 2);
   }
   /* GRU_A blocks (LDS / fp32 global path): per (wave, gate) chunk [k][64 lanes] */
   std::vector<float4> &ga_wf = H.ga_wf;
@@ -549,7 +553,7 @@ void build_lockstep_image(const Blob &B, const LoadEnv &env, HostModel &H)
   for (int w = 0; w < SAMPLE_WAVES && !reg; w++)
     for (int g = 0; g < 3; g++) {
       int K = gaK[w][g];
-      sa.ga_K[w][g] = K;
+      lt.ga_K[w][g] = K;
       std::vector<uint16_t> cbs(K * 8, int8 ? 0 : 0xFFFF);
       std::vector<uint32_t> wq(int8 ? K * 64 : 0, 0);
       size_t fbase = ga_wf.size();
@@ -569,12 +573,12 @@ void build_lockstep_image(const Blob &B, const LoadEnv &env, HostModel &H)
           }
         }
       }
-      if (int8) sa.ga_woff[w][g] = (int)(I.put(wq.data(), wq.size() * 4) / 4);
-      else sa.ga_woff[w][g] = (int)fbase;
-      sa.ga_coff[w][g] = (int)(I.put(cbs.data(), cbs.size() * 2) / 2);
+      if (int8) lt.ga_woff[w][g] = (int)(I.put(wq.data(), wq.size() * 4) / 4);
+      else lt.ga_woff[w][g] = (int)fbase;
+      lt.ga_coff[w][g] = (int)(I.put(cbs.data(), cbs.size() * 2) / 2);
     }
   I.align16();
-  sa.image_bytes = (int)img.size();
+  lt.image_bytes = (int)img.size();
 }
 
 void print_plan(bool mf_ok, const MfPlan &plan)
@@ -622,7 +626,9 @@ void build_mf_gru_b(const Blob &B, HostModel &H)
  * mfw_kernel) */
 void build_matrix_core_tables(const Blob &B, const ModelBuildOpts &opts, const LoadEnv &env, HostModel &H)
 {
-  SampleArgs &sa = H.sa;
+  MfTables &mt = H.sample.mf;
+  MfwTables &wt = H.sample.mfw;
+  SampleForm &form = H.sample.form;
   bool mf_ok = B.int8 && !H.sat && !env.no_mfma;
   /* the matrix-core GRU_B is a dense tile: a row block listing one block
    * position twice (find_idx_check accepts it, and sparse_sgemv_accum8x4
@@ -648,24 +654,24 @@ void build_matrix_core_tables(const Blob &B, const ModelBuildOpts &opts, const L
   if (!mf_ok) return;
   const int8_t *wa = (const int8_t *)B.ga.w;
   mf_tables(B.ga.blocks, B.ga.first, wa, plan, H.mf);
-  sa.mf_split = plan.split ? 1 : 0;
+  form.mf_split = plan.split ? 1 : 0;
   for (int g = 0; g < 3; g++) {
     H.mf_own[g] = plan.own[g];
     H.mf_pieces[g] = (int)plan.pieces[g].size();
   }
   for (int w = 0; w < SAMPLE_WAVES; w++) {
-    sa.mf_nzr[w] = plan.nzr[w];
-    sa.mf_nh[w] = plan.nh[w];
-    sa.mf_nfzr[w] = plan.nfzr[w];
-    sa.mf_nfh[w] = plan.nfh[w];
+    mt.mf_nzr[w] = plan.nzr[w];
+    mt.mf_nh[w] = plan.nh[w];
+    mt.mf_nfzr[w] = plan.nfzr[w];
+    mt.mf_nfh[w] = plan.nfh[w];
   }
   /* the wide kernel's split form (wide batches of split models) */
-  sa.mfw_split = 0;
+  form.mfw_split = 0;
   if (plan.split && H.plan_wide && !env.no_mfw_split && mfw_split_tables(B.ga.blocks, B.ga.first, wa, env.plan, H.mfw)) {
-    sa.mfw_split = 1;
+    form.mfw_split = 1;
     for (int w = 0; w < MFW_TAB_WAVES; w++) {
-      sa.mfw_nzr[w] = H.mfw.nzr[w];
-      sa.mfw_nh[w] = H.mfw.nh[w];
+      wt.mfw_nzr[w] = H.mfw.nzr[w];
+      wt.mfw_nh[w] = H.mfw.nh[w];
     }
   }
   build_mf_gru_b(B, H);
@@ -682,7 +688,7 @@ void build_matrix_core_tables(const Blob &B, const ModelBuildOpts &opts, const L
  * once per launch. */
 void build_range_bounds(const LoadEnv &env, HostModel &H)
 {
-  SampleArgs &sa = H.sa;
+  MfTables &mt = H.sample.mf;
   double bz = 0, bh = 0, ez = 0, eh = 0;
   bool finite = true;
   for (int i = 0; i < NA; i++)
@@ -707,14 +713,14 @@ void build_range_bounds(const LoadEnv &env, HostModel &H)
     (g < 2 ? ez : eh) = std::max(g < 2 ? ez : eh, e);
   }
   const double zr = 0.99 * (2147483648.0 / 16256.0) - bz - ez, hb = (double)kTanhFinBound - 0x1p17 - bh - eh;
-  sa.mf_zr_bound = finite && zr > 0 ? (float)zr : -1.f;
-  sa.mf_h_bound = finite && hb > 0 ? (float)hb : -1.f;
-  if (env.mf_exact) sa.mf_zr_bound = sa.mf_h_bound = -1.f;
-  if (env.mf_zr_bound) sa.mf_zr_bound = std::min(sa.mf_zr_bound, (float)atof(env.mf_zr_bound));
+  mt.mf_zr_bound = finite && zr > 0 ? (float)zr : -1.f;
+  mt.mf_h_bound = finite && hb > 0 ? (float)hb : -1.f;
+  if (env.mf_exact) mt.mf_zr_bound = mt.mf_h_bound = -1.f;
+  if (env.mf_zr_bound) mt.mf_zr_bound = std::min(mt.mf_zr_bound, (float)atof(env.mf_zr_bound));
   if (env.verbose) {
     char line[200];
-    snprintf(line, sizeof line, "lpcnet: GRU_A range bounds: z/r %g (bias+diag %g, embeddings %g), h %g\n", sa.mf_zr_bound, bz,
-             ez, sa.mf_h_bound);
+    snprintf(line, sizeof line, "lpcnet: GRU_A range bounds: z/r %g (bias+diag %g, embeddings %g), h %g\n", mt.mf_zr_bound, bz,
+             ez, mt.mf_h_bound);
     H.bounds_note += line;
   }
 }
@@ -744,7 +750,7 @@ void fp_pack_zr(float4 &lo, float4 &hi, int g, const float4 &v)
  * Sets the waves' slot counts and calls put(w, l, g, t, weights of the lane's
  * row in block t, column quad of block t) for every block of every lane. */
 template <typename Put>
-void fp_for_each_slot(const Blob &B, SampleArgs &sa, Put put)
+void fp_for_each_slot(const Blob &B, FpTables &ft, Put put)
 {
   const std::vector<std::vector<int>> &ga_blocks = B.ga.blocks;
   const float *wa = (const float *)B.ga.w;
@@ -754,8 +760,8 @@ void fp_for_each_slot(const Blob &B, SampleArgs &sa, Put put)
       kz = std::max(kz, (int)std::max(ga_blocks[w * 8 + j].size(), ga_blocks[NA / 8 + w * 8 + j].size()));
       kh = std::max(kh, (int)ga_blocks[2 * (NA / 8) + w * 8 + j].size());
     }
-    sa.fp_nzr[w] = kz;
-    sa.fp_nh[w] = kh;
+    ft.fp_nzr[w] = kz;
+    ft.fp_nh[w] = kh;
     for (int l = 0; l < 64; l++) {
       const int j = l >> 3, r = l & 7;
       for (int g = 0; g < 3; g++) {
@@ -777,7 +783,7 @@ void build_fp_short(const Blob &B, HostModel &H)
   H.fp_zr.assign((size_t)SAMPLE_WAVES * 2 * FP_ZF * 64, make_float4(nz, nz, nz, nz));
   H.fp_h.assign((size_t)SAMPLE_WAVES * FP_HF * 64, make_float4(nz, nz, nz, nz));
   H.fp_off.assign((size_t)SAMPLE_WAVES * FP_OFF_WORDS * 64, 0x60606060u); /* column quad NA/4 = 96: the +0 quad */
-  fp_for_each_slot(B, H.sa, [&](int w, int l, int g, int t, const float4 &v, uint32_t q) {
+  fp_for_each_slot(B, H.sample.fp, [&](int w, int l, int g, int t, const float4 &v, uint32_t q) {
     if (g < 2)
       fp_pack_zr(H.fp_zr[((size_t)w * 2 * FP_ZF + t) * 64 + l], H.fp_zr[((size_t)w * 2 * FP_ZF + FP_ZF + t) * 64 + l], g, v);
     else
@@ -804,7 +810,7 @@ void build_fp_long(const Blob &B, HostModel &H)
   H.fpl_zr.assign((size_t)SAMPLE_WAVES * KZ * 64 * 2, make_float4(nz, nz, nz, nz));
   H.fpl_h.assign((size_t)SAMPLE_WAVES * KH * 64, make_float4(nz, nz, nz, nz));
   H.fpl_off.assign((size_t)SAMPLE_WAVES * (KZ + KH) * 64, (uint32_t)(NA / 4) * 0x0101u); /* the +0 quad */
-  fp_for_each_slot(B, H.sa, [&](int w, int l, int g, int t, const float4 &v, uint32_t q) {
+  fp_for_each_slot(B, H.sample.fp, [&](int w, int l, int g, int t, const float4 &v, uint32_t q) {
     if (g < 2) {
       fp_pack_zr(H.fpl_zr[(((size_t)w * KZ + t) * 64 + l) * 2], H.fpl_zr[(((size_t)w * KZ + t) * 64 + l) * 2 + 1], g, v);
       uint32_t &o = H.fpl_off[((size_t)w * KZ + t) * 64 + l];
@@ -814,8 +820,8 @@ void build_fp_long(const Blob &B, HostModel &H)
       H.fpl_off[(size_t)SAMPLE_WAVES * KZ * 64 + ((size_t)w * KH + t) * 64 + l] = q;
     }
   });
-  H.sa.fpl_kz = KZ;
-  H.sa.fpl_kh = KH;
+  H.sample.fp.fpl_kz = KZ;
+  H.sample.fp.fpl_kh = KH;
 }
 
 void build_fp_tables(const Blob &B, const LoadEnv &env, HostModel &H)
@@ -838,7 +844,7 @@ void build_fp_tables(const Blob &B, const LoadEnv &env, HostModel &H)
   if (env.fp_force_long) fp_long = true;
   H.fp_ok = fp_ok;
   H.fp_long = fp_long;
-  H.sa.fp_long = fp_ok && fp_long ? 1 : 0;
+  H.sample.form.fp_long = fp_ok && fp_long ? 1 : 0;
   if (!fp_ok) return;
   if (fp_long) build_fp_long(B, H);
   else build_fp_short(B, H);
@@ -873,7 +879,7 @@ int choose_lockstep_lds(const ModelBuildOpts &opts, HostModel &H)
     set_err("model does not fit the 160 KiB LDS budget");
     return -1;
   }
-  H.sa.image_lds_bytes = H.image_lds;
+  H.sample.lockstep.image_lds_bytes = H.image_lds;
   return 0;
 }
 
@@ -941,7 +947,8 @@ void build_frame_tables(const Blob &B, HostModel &H)
 void build_info(const Blob &B, HostModel &H)
 {
   const int nba = H.nba, nbb = H.nbb;
-  const SampleArgs &sa = H.sa;
+  const MfTables &mt = H.sample.mf;
+  const SampleForm &form = H.sample.form;
   LPCNetModelInfo &in = H.info;
   in = LPCNetModelInfo{};
   in.variant = H.variant;
@@ -964,11 +971,11 @@ void build_info(const Blob &B, HostModel &H)
   H.mf_ga_ops = H.mf_gb_ops = 0;
   if (H.mf_ok) {
     double n4 = 0;
-    for (int w = 0; w < SAMPLE_WAVES; w++) n4 += 8.0 * (sa.mf_nzr[w] + sa.mf_nfzr[w]) + 4.0 * (sa.mf_nh[w] + sa.mf_nfh[w]);
+    for (int w = 0; w < SAMPLE_WAVES; w++) n4 += 8.0 * (mt.mf_nzr[w] + mt.mf_nfzr[w]) + 4.0 * (mt.mf_nh[w] + mt.mf_nfh[w]);
     H.mf_ga_ops = 2.0 * n4 * 1024.0;
     H.mf_gb_ops = 2.0 * 2.0 * MF_GB_TILES * 16384.0;
   }
-  in.long_rows = (H.mf_ok && sa.mf_split) || (H.fp_ok && sa.fp_long) ? 1 : 0;
+  in.long_rows = (H.mf_ok && form.mf_split) || (H.fp_ok && form.fp_long) ? 1 : 0;
   in.has_codebooks = H.cb_ok ? 1 : 0;
   in.lpc_gamma = H.mc.lpc_gamma;
   in.features_delay = H.mc.delay;
@@ -983,10 +990,11 @@ int build_host_model(const unsigned char *data, int len, const ModelBuildOpts &o
 {
   const LoadEnv env;
   Blob B;
-  memset(&H.sa, 0, sizeof(H.sa));
+  H.sample = SampleTables{};
   if (parse_model(data, len, opts, env, B, H)) return -1;
   build_gru_params(B, H);
   if (build_rcp(opts, env, H)) return -1;
+  build_fc_bound(B, env, H);
   build_lockstep_image(B, env, H);
   build_matrix_core_tables(B, opts, env, H);
   build_fp_tables(B, env, H);
@@ -997,7 +1005,7 @@ int build_host_model(const unsigned char *data, int len, const ModelBuildOpts &o
     const float *src[3] = {H.emb_sig, H.emb_pred, H.emb_exc};
     for (int t = 0; t < 3; t++) {
       H.mf_emb[t] = lane_ordered(src[t], H.mf.units);
-      if (H.sa.mfw_split) H.mfw_emb[t] = lane_ordered(src[t], H.mfw.units);
+      if (H.sample.form.mfw_split) H.mfw_emb[t] = lane_ordered(src[t], H.mfw.units);
     }
   }
   if (H.cb_ok) {
@@ -1012,15 +1020,19 @@ int build_host_model(const unsigned char *data, int len, const ModelBuildOpts &o
 std::vector<ModelUpload> model_uploads(const HostModel &h, ModelArgs &a)
 {
   memset(&a.fa, 0, sizeof(a.fa));
-  a.sa = h.sa;
+  a.sample = h.sample;
   a.da = DecodeArgs{};
   for (int i = 0; i < 4; i++) a.fa.ck_rep[i] = h.ck_rep[i];
   std::vector<ModelUpload> up;
   auto raw = [&](void *dst, const void *src, size_t bytes, bool present) { up.push_back(ModelUpload{dst, src, bytes, present}); };
   auto vec = [&](void *dst, const auto &v, bool present = true) { raw(dst, v.data(), v.size() * sizeof(v[0]), present); };
   FrameArgs &fa = a.fa;
-  SampleArgs &sa = a.sa;
-  const bool int8 = h.variant == LPCNET_VARIANT_INT8, mf = h.mf_ok, mfw = mf && h.sa.mfw_split;
+  SampleModel &sm = a.sample.model;
+  LockstepTables &lt = a.sample.lockstep;
+  MfTables &mt = a.sample.mf;
+  MfwTables &wt = a.sample.mfw;
+  FpTables &ft = a.sample.fp;
+  const bool int8 = h.variant == LPCNET_VARIANT_INT8, mf = h.mf_ok, mfw = mf && h.sample.form.mfw_split;
   vec(&fa.conv1_w, h.conv1_p);
   raw(&fa.conv1_b, h.conv1_b, COND * 4, true);
   vec(&fa.conv2_w, h.conv2_p);
@@ -1042,32 +1054,32 @@ std::vector<ModelUpload> model_uploads(const HostModel &h, ModelArgs &a)
   vec(&fa.ck_proj, h.ck_proj);
   raw(&fa.embed_pitch, h.embed_pitch, 256 * EP * 4, true);
   vec(&fa.rcp, h.rcp_dev);
-  raw(&sa.emb_sig, h.emb_sig, 256 * GA_ROWS * 4, true);
-  raw(&sa.emb_pred, h.emb_pred, 256 * GA_ROWS * 4, true);
-  raw(&sa.emb_exc, h.emb_exc, 256 * GA_ROWS * 4, true);
-  vec(&sa.ga_par, h.ga_par);
-  vec(&sa.ga_wsum, h.ga_wsum);
-  vec(&sa.gb_par, h.gb_par);
-  vec(&sa.gb_wsum, h.gb_wsum);
-  vec(&sa.image, h.img);
-  vec(&sa.mf, h.mf.tab, mf);
-  vec(&sa.mf_unit, h.mf.units, mf);
-  vec(&sa.mf_frow, h.mf.frow, mf);
-  vec(&sa.mfw_tab, h.mfw.tab, mfw);
-  vec(&sa.mfw_frow, h.mfw.frow, mfw);
-  vec(&sa.mfw_unit, h.mfw.units, mfw);
-  for (int t = 0; t < 3; t++) vec(&sa.mf_emb[t], h.mf_emb[t], mf);
-  for (int t = 0; t < 3; t++) vec(&sa.mfw_emb[t], h.mfw_emb[t], mfw);
-  vec(&sa.mf_gb, h.mf_gb, mf);
-  vec(&sa.fp_zr, h.fp_zr, h.fp_ok && !h.fp_long);
-  vec(&sa.fp_h, h.fp_h, h.fp_ok && !h.fp_long);
-  vec(&sa.fp_off, h.fp_off, h.fp_ok && !h.fp_long);
-  vec(&sa.fpl_zr, h.fpl_zr, h.fp_ok && h.fp_long);
-  vec(&sa.fpl_h, h.fpl_h, h.fp_ok && h.fp_long);
-  vec(&sa.fpl_off, h.fpl_off, h.fp_ok && h.fp_long);
-  vec(&sa.fp_gb, h.fp_gb, h.fp_ok);
-  vec(&sa.ga_wf, h.ga_wf, !int8);
-  raw(&sa.gb_recf, h.gbrec, 3 * NB * NB * 4, !int8);
+  raw(&sm.emb_sig, h.emb_sig, 256 * GA_ROWS * 4, true);
+  raw(&sm.emb_pred, h.emb_pred, 256 * GA_ROWS * 4, true);
+  raw(&sm.emb_exc, h.emb_exc, 256 * GA_ROWS * 4, true);
+  vec(&sm.ga_par, h.ga_par);
+  vec(&sm.ga_wsum, h.ga_wsum);
+  vec(&sm.gb_par, h.gb_par);
+  vec(&sm.gb_wsum, h.gb_wsum);
+  vec(&sm.image, h.img);
+  vec(&mt.mf, h.mf.tab, mf);
+  vec(&mt.mf_unit, h.mf.units, mf);
+  vec(&mt.mf_frow, h.mf.frow, mf);
+  vec(&wt.mfw_tab, h.mfw.tab, mfw);
+  vec(&wt.mfw_frow, h.mfw.frow, mfw);
+  vec(&wt.mfw_unit, h.mfw.units, mfw);
+  for (int t = 0; t < 3; t++) vec(&mt.mf_emb[t], h.mf_emb[t], mf);
+  for (int t = 0; t < 3; t++) vec(&wt.mfw_emb[t], h.mfw_emb[t], mfw);
+  vec(&mt.mf_gb, h.mf_gb, mf);
+  vec(&ft.fp_zr, h.fp_zr, h.fp_ok && !h.fp_long);
+  vec(&ft.fp_h, h.fp_h, h.fp_ok && !h.fp_long);
+  vec(&ft.fp_off, h.fp_off, h.fp_ok && !h.fp_long);
+  vec(&ft.fpl_zr, h.fpl_zr, h.fp_ok && h.fp_long);
+  vec(&ft.fpl_h, h.fpl_h, h.fp_ok && h.fp_long);
+  vec(&ft.fpl_off, h.fpl_off, h.fp_ok && h.fp_long);
+  vec(&ft.fp_gb, h.fp_gb, h.fp_ok);
+  vec(&lt.ga_wf, h.ga_wf, !int8);
+  raw(&sm.gb_recf, h.gbrec, 3 * NB * NB * 4, !int8);
   raw(&a.da.cb1, h.cb_ok ? h.cb[0]->data : nullptr, h.cb_ok ? h.cb[0]->size : 0, h.cb_ok);
   raw(&a.da.cb2, h.cb_ok ? h.cb[1]->data : nullptr, h.cb_ok ? h.cb[1]->size : 0, h.cb_ok);
   raw(&a.da.cb3, h.cb_ok ? h.cb[2]->data : nullptr, h.cb_ok ? h.cb[2]->size : 0, h.cb_ok);

@@ -17,6 +17,7 @@
 #include "lpcnet_engine.h"
 #include "lpcnet_mi355x.h"
 #include "mf_plan.h"
+#include "side_kernels.h" /* DecodeArgs */
 
 namespace lpcnet_mi355x {
 
@@ -79,7 +80,7 @@ struct ModelBuildOpts {
   int lds_extra[2][3] = {};
 };
 
-/* Everything a load computes.  The pointer members of sa are null; the
+/* Everything a load computes.  The pointer members of `sample` are null; the
  * const pointers below look into the blob, which must outlive the model. */
 struct HostModel {
   std::vector<Arr> records;
@@ -91,7 +92,7 @@ struct HostModel {
   int nba = 0, nbb = 0;
   std::vector<uint32_t> rcp_dev;
   bool rcp_custom = false; /* rcp_dev is not the default table */
-  SampleArgs sa;
+  SampleTables sample{}; /* the sample kernels' scalars, family by family, and the launchers' forms */
   int ck_rep[4] = {};
   LPCNetModelInfo info{}; /* the numbers that do not depend on the kernel choice */
   double mf_ga_ops = 0, mf_gb_ops = 0;
@@ -131,7 +132,7 @@ int build_host_model(const unsigned char *data, int len, const ModelBuildOpts &o
  * under lpcnet_mi355x_model_digest). */
 struct ModelArgs {
   FrameArgs fa;
-  SampleArgs sa;
+  SampleTables sample;
   DecodeArgs da;
 };
 /* struct ModelUpload: device_mem.h, beside DeviceTables::upload */

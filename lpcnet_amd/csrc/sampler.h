@@ -55,7 +55,7 @@ struct FcLane {
 
   /* factor*tanh(bias + w.x) of this lane, plus the other channel's term
    * (nnet.c:196-205: sum1 + sum2 through DPP quad_perm [1,0,3,2]).  FIN:
-   * the node sum is known finite and below kTanhFinBound (SampleArgs::fc_fin and
+   * the node sum is known finite and below kTanhFinBound (MfTables::fc_fin and
    * GRU_B states within [-2, 2]), tanh without its flush and NaN selects */
   template <bool FIN = false, bool HW = true>
   __device__ __forceinline__ float node_logit(float bias, float factor, const float *w, const float (&xv)[NB]) const

@@ -119,7 +119,7 @@ int lpcnet_mi355x::plc_launch(LPCNetBatch *b, const float *d_in, float *d_out, c
   a.out = d_out;
   a.active = d_active;
   a.rcp = b->fa.rcp;
-  a.rcp_hw = b->sa.rcp_hw;
+  a.rcp_hw = b->sample.form.rcp_hw;
   return timed_launch(b, TIMED_PLC, b->timing != 0, 1, "plc kernel launch failed", [&] { return launch_plc(a, b->stream); });
 }
 
@@ -758,7 +758,7 @@ static RdovaeArgs rdovae_args(const LPCNetBatch *b, int side, const unsigned cha
   a.active = d_active;
   a.cat = b->rdo.cat;
   a.rcp = b->fa.rcp;
-  a.rcp_hw = b->sa.rcp_hw;
+  a.rcp_hw = b->sample.form.rcp_hw;
   return a;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "model_host.h"
+#include "side_kernels.h"
 
 namespace lpcnet_mi355x {
 
@@ -27,7 +28,7 @@ void build_burg_tables(BurgTables &T);
 /* One compute_gruB layer `nm` of nin inputs under the rules of gru_init and
  * find_idx_check: its units from the bias record, and with `tables` the A
  * tiles of its input (the idx expanded with zero blocks) and recurrent
- * weights and the seeds (lpcnet_engine.h PlcArgs).  Units and inputs are
+ * weights and the seeds (side_kernels.h PlcArgs).  Units and inputs are
  * multiples of 64 up to PLC_DIM_MAX; int8 pairs that can saturate maddubs are
  * refused.  -1: set_err names the reason, prefixed with `who`. */
 int gru_tiles_parse(const std::vector<Arr> &L, const std::string &who, const std::string &nm, int nin, bool tables, int &units,

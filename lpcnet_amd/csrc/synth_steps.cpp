@@ -29,15 +29,17 @@ namespace {
 /* ---- the sample kernel of a launch ---------------------------------------- */
 /* What every sample launch takes from the batch: N samples for the nB states
  * at st.  Callers set cond, nframes, pcm, preload and stamps. */
-SampleArgs sample_args(const LPCNetBatch *b, StreamState *st, int nB, int N)
+SampleLaunch sample_args(const LPCNetBatch *b, StreamState *st, int nB, int N)
 {
-  SampleArgs sa = b->sa;
+  SampleLaunch sa{};
   sa.st = st;
   sa.delay = b->mc.delay;
   sa.nstreams = nB;
   sa.N = N;
   sa.preload = 0;
   sa.stamps = nullptr;
+  sa.trace_logits = b->trace_logits;
+  sa.trace_exc = b->trace_exc;
   sa.status = b->d_status;
   sa.spin_limit = b->spin_limit;
   return sa;
@@ -61,20 +63,24 @@ FrameArgs frame_args(const LPCNetBatch *b, StreamState *st, int nB, const float 
  * batch's: ensure_trace) */
 SampleKernel launch_kernel(const LPCNetBatch *b, int nB, bool preload, bool stamps)
 {
-  return kernel_for_launch(b->plan, nB, preload, b->sa.trace_logits != nullptr, stamps);
+  return kernel_for_launch(b->plan, nB, preload, b->trace_logits != nullptr, stamps);
 }
 
-int launch_sample_kernel(LPCNetBatch *b, const SampleArgs &sa)
+int launch_sample_kernel(LPCNetBatch *b, const SampleLaunch &sa)
 {
   if (sa.N <= 0) return 0;
+  const SampleTables &t = b->sample; /* each kernel: the launch, the model part, its family's tables */
   int rc = -1;
   switch (launch_kernel(b, sa.nstreams, sa.preload != 0, sa.stamps != nullptr)) {
-  case SampleKernel::FP: rc = launch_fp(sa, b->stream); break;
-  case SampleKernel::MFW: rc = launch_mfw(sa, b->plan.mfw_g, b->stream); break;
-  case SampleKernel::MF2: rc = launch_mf2(sa, b->stream); break;
-  case SampleKernel::MF: rc = launch_mf(sa, b->caps.S, mf_lds_bytes(b->caps.S, b->sa.mf_split), b->stream); break;
+  case SampleKernel::FP: rc = launch_fp(FpArgs{sa, t.model, t.fp}, t.form, b->stream); break;
+  case SampleKernel::MFW: rc = launch_mfw(MfwArgs{sa, t.model, t.mf, t.mfw}, t.form, b->plan.mfw_g, b->stream); break;
+  case SampleKernel::MF2: rc = launch_mf2(MfArgs{sa, t.model, t.mf}, t.form, b->stream); break;
+  case SampleKernel::MF:
+    rc = launch_mf(MfArgs{sa, t.model, t.mf}, t.form, b->caps.S, mf_lds_bytes(b->caps.S, t.form.mf_split), b->stream);
+    break;
   case SampleKernel::LOCKSTEP:
-    rc = launch_sample(sa, b->caps.S, b->variant, b->sat ? 1 : 0, b->caps.reg ? 1 : 0, b->caps.lds_bytes, b->stream);
+    rc = launch_sample(LockstepArgs{t.model, t.lockstep, sa}, b->caps.S, b->variant, b->sat ? 1 : 0, b->caps.reg ? 1 : 0,
+                       b->caps.lds_bytes, b->stream);
     break;
   }
   if (rc) {
@@ -131,7 +137,7 @@ int launch_frame_step(LPCNetBatch *b, const FrameStep &s)
   hipStream_t fs = ovl >= 0 ? b->fstream : b->stream;
   FrameArgs fa = frame_args(b, st, nB, s.d_features, s.d_lpc_frame);
   fa.keep_cond = s.keep_cond ? 1 : 0;
-  SampleArgs sa = sample_args(b, st, nB, N);
+  SampleLaunch sa = sample_args(b, st, nB, N);
   sa.pcm = s.d_pcm;
   sa.preload = std::max(0, std::min(s.preload, N));
   sa.stamps = b->d_stamps;
@@ -189,10 +195,10 @@ int launch_frame_step(LPCNetBatch *b, const FrameStep &s)
  * (chunk_kernel, outputs in d_chunk[f]); launch the sample kernel of frames
  * f .. f + nfr - 1 on b->stream, reading their conditioning from d_chunk[f..]
  * and writing d_pcm [nfr][B][N].  nfr > 1: matrix-core kernel only, every
- * stream past its first `delay` frames (SampleArgs::nframes). */
+ * stream past its first `delay` frames (SampleLaunch::nframes). */
 int launch_chunk_samples(LPCNetBatch *b, int f, short *d_pcm, int N, int nfr = 1)
 {
-  SampleArgs sa = sample_args(b, b->d_state, b->B, N);
+  SampleLaunch sa = sample_args(b, b->d_state, b->B, N);
   sa.cond = b->d_chunk + (size_t)f * b->B;
   sa.nframes = nfr;
   sa.pcm = d_pcm;
@@ -259,7 +265,7 @@ static int launch_single_frame_chunked(LPCNetBatch *b, int nB, const float *d_fe
     return -1;
   }
   b->frames_done(1);
-  SampleArgs sa = sample_args(b, b->d_state, nB, N);
+  SampleLaunch sa = sample_args(b, b->d_state, nB, N);
   sa.cond = nullptr;
   sa.nframes = 1;
   sa.pcm = d_pcm;
@@ -362,7 +368,7 @@ int lpcnet_mi355x::synth_first(LPCNetBatch *b, int nB, const float *features, sh
   const bool own_call = !staged && !pre;
   const ChoiceEnv env = own_call ? choice_env_from_env() : ChoiceEnv();
   if (own_call &&
-      single_frame_chunked(b->plan, b->chunking, nB, N, preload, b->sa.trace_logits != nullptr, b->d_stamps != nullptr, env)) {
+      single_frame_chunked(b->plan, b->chunking, nB, N, preload, b->trace_logits != nullptr, b->d_stamps != nullptr, env)) {
     /* the caller's buffers through pinned staging: both copies truly
      * asynchronous, one synchronisation per frame.  Features already in the
      * batch's own pinned buffer (lpcnet_batch_host_features) skip the host
@@ -626,7 +632,7 @@ LPCNET_EXPORT int lpcnet_batch_synthesize_frames(LPCNetBatch *b, const float *h_
   if (ensure_trace(b, N)) return -1;
   const size_t fstride = (size_t)b->B * NF;
   if (nframes == 0) return 0;
-  const FramePath path = frame_path(b->plan, b->B, b->fstream != nullptr, b->chunking, b->sa.trace_logits != nullptr,
+  const FramePath path = frame_path(b->plan, b->B, b->fstream != nullptr, b->chunking, b->trace_logits != nullptr,
                                     b->d_stamps != nullptr, nframes, N, choice_env_from_env());
   const bool mfm = path.multi_frame, ovl = path.overlapped, chunked = path.chunked;
   if (ovl) {

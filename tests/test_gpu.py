@@ -370,7 +370,7 @@ def test_restore_refuses_out_of_range_gru_state(require_gpu, blobs):
 @pytest.mark.parametrize("mf2", ["0", "1"])
 def test_walk_exact_form_for_states_outside_the_bound(require_gpu, blobs, monkeypatch, mf2):
     """The dual-FC walk takes its select-free tanh only when the model's node
-    sums are bounded (SampleArgs::fc_fin) and every GRU_B state of the
+    sums are bounded (MfTables::fc_fin) and every GRU_B state of the
     workgroup lies within [-2, 2] at launch.  A restored NaN GRU_B state
     (accepted by restore) must send that workgroup through the exact x86
     form: the same PCM as with the exact form forced (LPCNET_FC_EXACT)."""
@@ -616,7 +616,7 @@ def test_chunked_frame_network_equals_per_frame(require_gpu, blobs, B, name):
 @pytest.mark.parametrize("B,mfw", [(1, "0"), (2, "0"), (70, "0"), (256, "0"), (1030, "0"), (1030, "1"), (2100, "1")])
 def test_multi_frame_sample_launches_match_per_frame(require_gpu, blobs, monkeypatch, B, mfw):
     """lpcnet_batch_synthesize_frames on the matrix-core kernel launches the
-    sample kernel once per chunk of frames (SampleArgs::nframes), carrying the
+    sample kernel once per chunk of frames (SampleLaunch::nframes), carrying the
     states in registers across frames.  Against the per-frame launches
     (LPCNET_NO_MULTIFRAME) over runs that start at a reset (the FEATURES_DELAY
     frames go to single-frame launches), follow a per-stream reset and a

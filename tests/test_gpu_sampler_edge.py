@@ -35,7 +35,7 @@ A launch with teacher-forced samples or tracing takes mf_kernel on the mf2 /
 mfw batches (kernel_choice.cpp), so those runs also hand the sampler state
 from one kernel to the other and back.
 
-The walk form (select-free or exact tanh, SampleArgs::fc_fin) and the GRU_A
+The walk form (select-free or exact tanh, MfTables::fc_fin) and the GRU_A
 range bounds are read from the engine's LPCNET_VERBOSE lines: fc_mid and
 fc_ramp must walk exactly, and ga_hbias's h conditioning must lie outside the
 h bound.  ga_hbias and ga_zrbias put single GRU_A units out of range, one

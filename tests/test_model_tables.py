@@ -11,7 +11,7 @@ layout on purpose regenerates the fixture with
     python tests/test_model_tables.py tests/golden/model_digests.json
 
 and says so.  Regenerated once since: entry 0 (the sample kernels' scalar
-block) of the int8 and int8_skewed models moved when SampleArgs::mf_h_bound
+block) of the int8 and int8_skewed models moved when MfTables::mf_h_bound
 went from 1e17 to the select-free tanh's true domain (device_math.h
 kTanhFinBound less the other h-input terms); no table moved.
 """

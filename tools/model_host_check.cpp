@@ -114,7 +114,7 @@ static void compare(const Mat &D, const Mat &R, const char *what, const char *ta
 
 static void check_mf(const HostModel &H, const Mat &R, const char *tag)
 {
-  const SampleArgs &sa = H.sa;
+  const MfTables &mt = H.sample.mf;
   Mat D(R.size(), 0);
   CHECK(H.mf.tab.size() == (size_t)SAMPLE_WAVES * MF_LANE_U32 * 64 && H.mf.units.size() == (size_t)SAMPLE_WAVES * 64 &&
             H.mf.frow.size() == (size_t)3 * SAMPLE_WAVES * 64,
@@ -123,15 +123,15 @@ static void check_mf(const HostModel &H, const Mat &R, const char *tag)
   CHECK((int)units.size() == NA && *units.begin() == 0 && *units.rbegin() == NA - 1, "%s: mf_unit is not a permutation", tag);
   std::set<int> merged[3], hosted[3]; /* unit blocks whose lanes merge pieces / that pieces go to */
   for (int w = 0; w < SAMPLE_WAVES; w++) {
-    CHECK(4 * (sa.mf_nzr[w] + sa.mf_nfzr[w]) <= MF_ZMAX, "%s: wave %d z/r groups %d + %d", tag, w, sa.mf_nzr[w], sa.mf_nfzr[w]);
-    CHECK(4 * (sa.mf_nh[w] + sa.mf_nfh[w]) <= MF_HMAX, "%s: wave %d h groups %d + %d", tag, w, sa.mf_nh[w], sa.mf_nfh[w]);
-    CHECK(sa.mf_split || (sa.mf_nfzr[w] == 0 && sa.mf_nfh[w] == 0), "%s: hosted groups in an unsplit plan", tag);
+    CHECK(4 * (mt.mf_nzr[w] + mt.mf_nfzr[w]) <= MF_ZMAX, "%s: wave %d z/r groups %d + %d", tag, w, mt.mf_nzr[w], mt.mf_nfzr[w]);
+    CHECK(4 * (mt.mf_nh[w] + mt.mf_nfh[w]) <= MF_HMAX, "%s: wave %d h groups %d + %d", tag, w, mt.mf_nh[w], mt.mf_nfh[w]);
+    CHECK(H.sample.form.mf_split || (mt.mf_nfzr[w] == 0 && mt.mf_nfh[w] == 0), "%s: hosted groups in an unsplit plan", tag);
     const uint32_t *wtab = &H.mf.tab[(size_t)w * MF_LANE_U32 * 64];
     for (int l = 0; l < 64; l++) {
       const int unit = H.mf.units[w * 64 + l];
       CHECK(unit % 8 == l % 8 && unit / 8 == H.mf.units[w * 64 + (l & ~7)] / 8, "%s: lane %d of wave %d unit %d", tag, l, w, unit);
       for (int g = 0; g < 3; g++) {
-        const int nown = 4 * (g < 2 ? sa.mf_nzr[w] : sa.mf_nh[w]), nfor = 4 * (g < 2 ? sa.mf_nfzr[w] : sa.mf_nfh[w]);
+        const int nown = 4 * (g < 2 ? mt.mf_nzr[w] : mt.mf_nh[w]), nfor = 4 * (g < 2 ? mt.mf_nfzr[w] : mt.mf_nfh[w]);
         const int fr = H.mf.frow[((size_t)g * SAMPLE_WAVES + w) * 64 + l], target = fr & 0xFFFF;
         if (fr >> 16) merged[g].insert(unit / 8);
         /* a gate without pieces: no lane merges, no lane hosts (z and r share their group counts, so a
@@ -157,7 +157,7 @@ static void check_mf(const HostModel &H, const Mat &R, const char *tag)
 static void check_mfw(const HostModel &H, const Mat &R, const char *tag)
 {
   constexpr int FS = SAMPLE_THREADS + 64 * MFW_H_WAVES;
-  const SampleArgs &sa = H.sa;
+  const MfwTables &wt = H.sample.mfw;
   const MfwSplitTab &T = H.mfw;
   Mat D(R.size(), 0);
   CHECK(T.tab.size() == (size_t)MFW_TAB_WAVES * MF_LANE_U32 * 64 && T.units.size() == (size_t)SAMPLE_THREADS &&
@@ -178,9 +178,9 @@ static void check_mfw(const HostModel &H, const Mat &R, const char *tag)
       unit_of[pr] = T.units[t];
     }
     for (int w = 0; w < MFW_TAB_WAVES; w++) {
-      const int n = 4 * (g < 2 ? sa.mfw_nzr[w] : sa.mfw_nh[w]);
+      const int n = 4 * (g < 2 ? wt.mfw_nzr[w] : wt.mfw_nh[w]);
       CHECK(n >= 4 && n <= (g < 2 ? MF_ZMAX : MF_HMAX), "%s: table wave %d gate %d slots %d", tag, w, g, n);
-      CHECK(sa.mfw_nzr[w] == T.nzr[w] && sa.mfw_nh[w] == T.nh[w], "%s: table wave %d group counts", tag, w);
+      CHECK(wt.mfw_nzr[w] == T.nzr[w] && wt.mfw_nh[w] == T.nh[w], "%s: table wave %d group counts", tag, w);
       const uint32_t *wtab = &T.tab[(size_t)w * MF_LANE_U32 * 64];
       for (int l = 0; l < 64; l++) {
         int row = -1;
@@ -305,13 +305,15 @@ static void check_model(const char *name, const unsigned char *blob, int n, int 
         CHECK(false, "%s: build failed: %s", tag, last_err().c_str());
         continue;
       }
+      const SampleForm &form = H.sample.form;
+      const MfTables &mt = H.sample.mf;
       if (report) {
         printf("plan %s: variant %d may_saturate %d mf_ok %d fp_ok %d fp_long %d lockstep_streams %d", tag, H.variant, H.sat, H.mf_ok,
                H.fp_ok, H.fp_long, H.S);
         if (H.mf_ok) {
-          printf(" split %d wide_split %d own %d %d %d pieces %d %d %d groups", H.sa.mf_split, H.sa.mfw_split, H.mf_own[0], H.mf_own[1],
+          printf(" split %d wide_split %d own %d %d %d pieces %d %d %d groups", form.mf_split, form.mfw_split, H.mf_own[0], H.mf_own[1],
                  H.mf_own[2], H.mf_pieces[0], H.mf_pieces[1], H.mf_pieces[2]);
-          for (int w = 0; w < SAMPLE_WAVES; w++) printf(" (%d %d %d %d)", H.sa.mf_nzr[w], H.sa.mf_nfzr[w], H.sa.mf_nh[w], H.sa.mf_nfh[w]);
+          for (int w = 0; w < SAMPLE_WAVES; w++) printf(" (%d %d %d %d)", mt.mf_nzr[w], mt.mf_nfzr[w], mt.mf_nh[w], mt.mf_nfh[w]);
         }
         printf("\n");
       }
@@ -321,14 +323,14 @@ static void check_model(const char *name, const unsigned char *blob, int n, int 
         declined++;
         continue;
       }
-      CHECK(!force || H.sa.mf_split, "%s: plan not split", tag);
-      CHECK(H.sa.mfw_split == (H.sa.mf_split && c.wide && wide_split_exists(A) ? 1 : 0), "%s: wide split form %d", tag, H.sa.mfw_split);
+      CHECK(!force || form.mf_split, "%s: plan not split", tag);
+      CHECK(form.mfw_split == (form.mf_split && c.wide && wide_split_exists(A) ? 1 : 0), "%s: wide split form %d", tag, form.mfw_split);
       check_mf(H, R, tag);
-      if (H.sa.mfw_split) check_mfw(H, R, tag);
+      if (form.mfw_split) check_mfw(H, R, tag);
       check_gru_b(H, tag);
       plans++;
-      split_plans += H.sa.mf_split;
-      wide_plans += H.sa.mfw_split;
+      split_plans += form.mf_split;
+      wide_plans += form.mfw_split;
     }
   }
   unsetenv("LPCNET_MF_FORCE_SPLIT");

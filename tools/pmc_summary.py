@@ -78,7 +78,7 @@ def bench_line(log):
 def kernel_match(short, full):
     """bench's ModelInfo.kernel_name ('mf_kernel<4, 0, false, true>') in a
     rocprofv3 kernel name ('void lpcnet_mi355x::mf_kernel<4, 0, false,
-    true>(lpcnet_mi355x::SampleArgs)'), spacing-insensitive"""
+    true>(lpcnet_mi355x::MfArgs)'), spacing-insensitive"""
     return short.replace(" ", "") in full.replace(" ", "")
 
 
