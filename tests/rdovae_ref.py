@@ -119,6 +119,14 @@ class RdoEnc(_Net):
     def save(self) -> bytes:
         return self.gru_bytes() + self.mem.tobytes()
 
+    def restore(self, st: bytes):
+        v, p = np.frombuffer(st, np.float32), 0
+        for i, g in enumerate(self.grus):
+            self.states[i] = v[p:p + g.n].copy()
+            p += g.n
+        assert v.size - p == self.mem.size
+        self.mem = v[p:].copy()
+
 
 class RdoDec(_Net):
     """One stream's RDOVAEDecState, dec_init_states and decode_qframe."""
