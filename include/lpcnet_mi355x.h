@@ -596,13 +596,14 @@ LPCNET_EXPORT int lpcnet_batch_encode_restore_state(LPCNetBatch *b, int stream, 
 LPCNET_EXPORT int lpcnet_mi355x_enc_main_pitch(const float *center_pitch, int *out, int n);
 
 /* ---- Concealment machine (lpcnet_plc_update / lpcnet_plc_conceal) -----------
- * lpcnet_plc.c:188-337, 495-503 for a whole batch, one call per 10 ms tick:
+ * lpcnet_plc.c:188-503 for a whole batch, one call per 10 ms tick, in the
+ * reference's three modes (causal, non-causal, codec):
  * every stream s has the semantics of one reference LPCNetPLCState (built, as
  * the reference ships, with PLC_SKIP_UPDATES defined), bit-identical in the
  * PCM of every tick and in its state to the same stream run alone.  Streams
  * that received their packet and streams that lost it share the call.  The
  * control state (pcm_fill, skip_analysis, blend, loss_count, the FEC queue's
- * positions, the deferred-feature fill) depends on the sequence of lost and
+ * positions, the deferred-feature fill, queued_update) depends on the sequence of lost and
  * received ticks and FEC adds alone, so the host plans a tick for every stream
  * without reading anything back; all of a tick's work is queued on the
  * batch's stream and nothing synchronises between its steps.  The machine's
@@ -615,18 +616,32 @@ LPCNET_EXPORT int lpcnet_mi355x_enc_main_pitch(const float *center_pitch, int *o
  * lpcnet_batch_set_model_constants changed it is refused (close and reopen).
  * lpcnet_batch_load_model closes the machine.  lpcnet_batch_reset /
  * _reset_stream also reset the machine's streams.
- * Out of scope: the non-causal mode (lpcnet_plc.c:342-492), the #else
- * branches of PLC_SKIP_UPDATES, an fp32 predictor, drop-in LPCNetPLCState
+ * The non-causal mode (lpcnet_plc.c:339-492) delays its output by 80 samples
+ * and, on the first received tick after a loss, synthesises backwards over
+ * the received frame to cross-fade into it.  Like the reference it exists
+ * only for models with FEATURES_DELAY 0 (the reference exits otherwise,
+ * :357-361): an open on a batch with another delay is refused.  Its control
+ * state is loss_count and queued_update alone; it never reads the FEC queue,
+ * though fec_add / fec_clear still move the queue's positions.  Every received
+ * tick runs a full 160-sample teacher-forced synthesis (this branch has no
+ * PLC_SKIP_UPDATES shortcut); the first received tick after a loss runs 320
+ * speculative samples and queues 160 more for the next tick.  Its extra
+ * per-stream data (queued_samples, dc_buf, the saved synthesis state) is
+ * allocated by the open of that mode only.
+ * Out of scope: the #else branches of PLC_SKIP_UPDATES, the disabled
+ * alternative of :419-422, an fp32 predictor, drop-in LPCNetPLCState
  * handles.  Received frames on which burg_cepstral_analysis aborts in the
  * reference (all-zero half-frames) are outside the contract, as above.
  * Every refusal returns -1 with the reason in lpcnet_mi355x_last_error and
  * launches nothing. */
-#define LPCNET_CONCEAL_CAUSAL    0 /* the values of the reference's LPCNET_PLC_*; LPCNET_PLC_NONCAUSAL (1) is refused */
+#define LPCNET_CONCEAL_CAUSAL    0 /* the values of the reference's LPCNET_PLC_* */
+#define LPCNET_CONCEAL_NONCAUSAL 1 /* FEATURES_DELAY 0 only */
 #define LPCNET_CONCEAL_CODEC     2
 #define LPCNET_CONCEAL_DC_FILTER 4
 /* lpcnet_plc_init + lpcnet_plc_reset for every stream (the synthesis,
  * predictor and analysis states are reset too).  Needs a model with usable PLC
- * records; one machine per batch. */
+ * records; one machine per batch.  LPCNET_CONCEAL_NONCAUSAL on a batch whose
+ * FEATURES_DELAY is not 0: -1, "non-causal ... FEATURES_DELAY". */
 LPCNET_EXPORT int lpcnet_batch_conceal_open(LPCNetBatch *b, int options);
 LPCNET_EXPORT int lpcnet_batch_conceal_close(LPCNetBatch *b);
 LPCNET_EXPORT int lpcnet_batch_conceal_reset(LPCNetBatch *b, int stream /* lpcnet_plc_reset; -1: all */);
@@ -649,13 +664,19 @@ LPCNET_EXPORT int lpcnet_batch_conceal_fec_clear(LPCNetBatch *b, int stream);
  * fec_skip, feature_buffer_fill; features [20] = st->features; pcm_buf
  * [FEATURES_DELAY * 160 + 240] = st->pcm; dc [2] = dc_mem, syn_dc */
 LPCNET_EXPORT int lpcnet_batch_conceal_get_state(LPCNetBatch *b, int stream, int *ctrl, float *features, short *pcm_buf, double *dc);
+/* the non-causal mode's own state, after a synchronisation; any pointer may be
+ * NULL: queued_update, queued_samples [160], dc_buf [80].  -1 when the open
+ * machine is in another mode. */
+LPCNET_EXPORT int lpcnet_batch_conceal_get_state_noncausal(LPCNetBatch *b, int stream, int *queued_update, short *queued_samples,
+                                                           short *dc_buf);
 /* Host only: the machine's planner on one stream from reset over nticks ticks.
  * lost [nticks]; fec_adds [nticks] (NULL: none): before tick t, n > 0 adds,
  * -1 a NULL add, -2 a clear.  steps (NULL: count only) receives up to
  * max_steps triples (op, a, b) -- the primitive calls of lpcnet_plc.c in order,
  * see conceal_plan.h -- tick_end [nticks] (NULL: not wanted) the number of
  * steps up to and including each tick, ctrl [nticks][9] (NULL: not wanted) the
- * control fields after each tick.  Returns the number of steps. */
+ * control fields after each tick.  Returns the number of steps.  The non-causal
+ * mode at a features_delay other than 0 is refused as the open refuses it. */
 LPCNET_EXPORT int lpcnet_mi355x_conceal_plan(int options, int features_delay, const unsigned char *lost, const int *fec_adds,
                                              int nticks, int *steps, int max_steps, int *tick_end, int *ctrl);
 

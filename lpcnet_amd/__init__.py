@@ -36,6 +36,7 @@ PLC_ROW_FEATURES = 2  # LPCNET_PLC_ROW_FEATURES
 VARIANT_INT8 = 0
 VARIANT_FP32 = 1
 CONCEAL_CAUSAL = 0     # LPCNET_CONCEAL_*: the reference's LPCNET_PLC_* values
+CONCEAL_NONCAUSAL = 1  # FEATURES_DELAY 0 only
 CONCEAL_CODEC = 2
 CONCEAL_DC_FILTER = 4
 CONCEAL_CTRL = ("pcm_fill", "skip_analysis", "blend", "loss_count", "fec_fill_pos", "fec_read_pos", "fec_keep_pos",
@@ -186,6 +187,7 @@ def _load():
         "lpcnet_batch_conceal_fec_add": (i, [vp, i, vp]),
         "lpcnet_batch_conceal_fec_clear": (i, [vp, i]),
         "lpcnet_batch_conceal_get_state": (i, [vp, i, vp, vp, vp, vp]),
+        "lpcnet_batch_conceal_get_state_noncausal": (i, [vp, i, vp, vp, vp]),
         "lpcnet_mi355x_conceal_plan": (i, [i, i, vp, vp, i, vp, i, vp, vp]),
     }
     for name, (res, args) in sig.items():
@@ -1042,9 +1044,10 @@ class LPCNetBatch:
 
     # -- concealment machine (lpcnet_plc_update / lpcnet_plc_conceal) --------
     def conceal_open(self, options: int = CONCEAL_CAUSAL) -> None:
-        """lpcnet_plc_init + lpcnet_plc_reset for every stream: CONCEAL_CAUSAL
-        or CONCEAL_CODEC, with or without CONCEAL_DC_FILTER.  Needs a model
-        with PLC records."""
+        """lpcnet_plc_init + lpcnet_plc_reset for every stream: CONCEAL_CAUSAL,
+        CONCEAL_NONCAUSAL or CONCEAL_CODEC, with or without CONCEAL_DC_FILTER.
+        Needs a model with PLC records; CONCEAL_NONCAUSAL also FEATURES_DELAY 0
+        (set_model_constants or the blob's record)."""
         if lib.lpcnet_batch_conceal_open(self._b, options) != 0:
             raise LPCNetError(last_error())
 
@@ -1105,6 +1108,17 @@ class LPCNetBatch:
         out = dict(zip(CONCEAL_CTRL, (int(v) for v in ctrl)))
         out.update(features=f, pcm=p[:self.info().features_delay * FRAME_SIZE + 240].copy(), dc_mem=float(dc[0]), syn_dc=float(dc[1]))
         return out
+
+    def conceal_state_noncausal(self, stream: int) -> dict:
+        """What the non-causal mode keeps beside conceal_state(): queued_update,
+        queued_samples [160] int16, dc_buf [80] int16.  LPCNetError when the
+        open machine is in another mode."""
+        q = C.c_int(0)
+        qs = np.zeros(FRAME_SIZE, np.int16)
+        db = np.zeros(FRAME_SIZE // 2, np.int16)
+        if lib.lpcnet_batch_conceal_get_state_noncausal(self._b, stream, C.addressof(q), qs.ctypes.data, db.ctypes.data) != 0:
+            raise LPCNetError(last_error())
+        return {"queued_update": int(q.value), "queued_samples": qs, "dc_buf": db}
 
     # -- device-resident path (benchmarks) ---------------------------------
     def device_alloc(self, nbytes: int) -> int:

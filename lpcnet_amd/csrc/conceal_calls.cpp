@@ -1,8 +1,8 @@
 /*
  * conceal_calls.cpp -- the concealment machine of a batch
  * (lpcnet_batch_conceal_*): lpcnet_plc_update / lpcnet_plc_conceal
- * (lpcnet_plc.c:188-337, 495-503, causal and codec modes) for every stream of
- * a batch in one call per tick, streams that received their packet and
+ * (lpcnet_plc.c:188-503, causal, codec and non-causal modes) for every stream
+ * of a batch in one call per tick, streams that received their packet and
  * streams that lost it side by side.
  *
  * The control state of every stream lives on the host and is advanced by the
@@ -16,7 +16,9 @@
  * synthesis steps on work states: the group's StreamStates gathered into the
  * first n slots of a work array, the step run there (the *_first_device
  * steps of synth_steps.cpp), the states scattered back -- or not, which is the
- * reference's struct copy and restore around a speculative synthesis.
+ * reference's struct copy and restore around a speculative synthesis.  The
+ * non-causal mode's copy spans three synthesis calls (:384-414): there the
+ * states are saved into an array of their own and put back by explicit steps.
  * Nothing synchronises between the steps or at the end of the device form.
  *
  * The index lists and masks of a tick are written into pinned memory and
@@ -28,6 +30,7 @@
 
 #include <array>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "batch.h"
@@ -47,6 +50,7 @@ struct ConcealMachine {
   ConcealData d{};
   DevPtr<char> base;             /* the carved device buffer */
   StreamState *work = nullptr;   /* [B] the states a synthesis step runs on */
+  StreamState *spec = nullptr;   /* [B] lpcnet_plc_update_non_causal's copy (:384, :414); that mode only */
   short *io = nullptr;           /* [B][FRAME] the host form's PCM */
   std::vector<ConcealCtrl> ctrl; /* [B] */
   int ulaw0 = 0;                 /* lin2ulaw(0.f) */
@@ -99,7 +103,7 @@ bool needs_mask(int op) { return op == CO_BURG || op == CO_ANALYSIS || op == CO_
 int plan_batch_tick(const ConcealMachine &M, int B, const unsigned char *lost, const unsigned char *active,
                     std::vector<ConcealCtrl> &ctrl, TickPlan &T)
 {
-  using Key = std::array<int, CONCEAL_CTRL_INTS + 1>;
+  using Key = std::array<int, CONCEAL_STATE_INTS + 1>;
   struct Class {
     std::vector<int> members;
     std::vector<ConcealStep> steps;
@@ -111,12 +115,12 @@ int plan_batch_tick(const ConcealMachine &M, int B, const unsigned char *lost, c
     if (active && !active[s]) continue;
     Key k;
     memcpy(k.data(), &ctrl[s], sizeof(ConcealCtrl));
-    k[CONCEAL_CTRL_INTS] = lost[s] != 0;
+    k[CONCEAL_STATE_INTS] = lost[s] != 0;
     auto it = index.find(k);
     if (it == index.end()) {
       Class c;
       c.after = ctrl[s];
-      if (plan_tick(c.after, lost[s] != 0, M.options, M.d.delay, c.steps) || !conceal_ctrl_ok(c.after, M.d.delay)) {
+      if (plan_tick(c.after, lost[s] != 0, M.options, M.d.delay, c.steps) || !conceal_ctrl_ok(c.after, M.d.delay, M.options)) {
         set_err("conceal: the planner left its invariants");
         return -1;
       }
@@ -202,31 +206,65 @@ int glue(int rc, const char *what)
   return rc;
 }
 
+/* rows of shorts, one per stream: where a synthesis step takes its teacher
+ * forcing from or puts its samples */
+struct PcmRows {
+  short *p = nullptr;
+  int stride = 0, off = 0;
+};
+
 /* a synthesis step of a group: its states into the work array, the step
  * there, its PCM where the step says, the states back unless speculative */
 int synth_step(LPCNetBatch *b, ConcealMachine &M, const ConcealStep &st, const int *idx, int n, short *d_pcm)
 {
   const ConcealData &d = M.d;
+  const int N = st.a, row = d.buf + FRAME;
   if (launch_state_copy(M.work, b->d_state, nullptr, idx, n, b->stream)) { set_err("conceal: state gather failed"); return -1; }
   bool commit = true;
   if (st.op == CO_FLUSH) {
-    if (glue(launch_conceal_gather(d, idx, n, b->d_feat, st.a, nullptr, nullptr, 0, 0, 0, b->stream), "gather")) return -1;
-    if (frame_first_device(b, n, b->d_feat, true, M.work)) return -1;
-  } else if (st.op == CO_TAIL) {
-    if (tail_first_device(b, n, b->d_pcm, st.a, 0, M.work)) return -1;
-    if (glue(launch_conceal_scatter(d, idx, n, b->d_pcm, d_pcm, 0, st.a, b->stream), "scatter")) return -1;
-  } else { /* CO_IMPL */
-    const int N = st.a;
-    const bool from_buf = st.b == CI_BUF, pre = from_buf || st.b == CI_PCM_PRE;
-    if (glue(launch_conceal_gather(d, idx, n, b->d_feat, -1, pre ? b->d_pcm : nullptr, d_pcm, from_buf, 0, N, b->stream), "gather"))
+    if (st.a < 0 || st.a >= CONCEAL_DEFER) { set_err("conceal: a flush pass outside the deferred buffer"); return -1; }
+    if (glue(launch_conceal_gather_rows(idx, n, b->d_feat, d.defer + (size_t)st.a * NF, CONCEAL_DEFER * NF, nullptr, nullptr, 0, 0, b->stream),
+             "gather"))
       return -1;
-    if (synth_first_device(b, n, b->d_feat, b->d_pcm, N, pre ? N : 0, M.work)) return -1;
-    if (st.b == CI_SPEC) {
-      if (glue(launch_conceal_scatter(d, idx, n, b->d_pcm, nullptr, 0, N, b->stream), "scatter")) return -1;
-      commit = false;
-    } else if (st.b == CI_PCM_OUT) {
-      if (glue(launch_conceal_scatter(d, idx, n, b->d_pcm, d_pcm, FRAME - N, N, b->stream), "scatter")) return -1;
+    if (frame_first_device(b, n, b->d_feat, true, M.work)) return -1;
+  } else {
+    const float *feat = d.features;
+    int feat_stride = NF;
+    PcmRows pre, out;
+    if (st.op == CO_TAIL) {
+      feat = nullptr;
+      switch (st.b) {
+      case CT_PCM: out = {d_pcm, FRAME, 0}; break;
+      case CT_REV: out = {d.rev, FRAME, 0}; break;
+      case CT_PCM_PRE: pre = {d_pcm, FRAME, 0}; break;
+      case CT_PCM_HI: out = {d_pcm, FRAME, FRAME / 2}; break;
+      default: set_err("conceal: unknown tail step"); return -1;
+      }
+    } else { /* CO_IMPL */
+      switch (st.b) {
+      case CI_BUF: pre = {d.pcm, row, 0}; break;
+      case CI_SPEC: out = {d.tmp, FRAME / 2, 0}; commit = false; break;
+      case CI_PCM_PRE: pre = {d_pcm, FRAME, 0}; break;
+      case CI_PCM_OUT: out = {d_pcm, FRAME, FRAME - N}; break;
+      case CI_QUEUE: pre = {d.queued, FRAME, 0}; break;
+      case CI_BUF_OUT: out = {d.pcm, row, FRAME / 2}; break;
+      case CI_REV: pre = {d.rev, FRAME, 0}; break;
+      case CI_ANALYSED: feat = d.rows + BURG_N; feat_stride = PLC_IN; pre = {d.pcm, row, FRAME / 2}; break;
+      case CI_BUF_HI: pre = {d.pcm, row, FRAME / 2}; break;
+      case CI_PCM_LO: out = {d_pcm, FRAME, 0}; break;
+      default: set_err("conceal: unknown synthesis step"); return -1;
+      }
     }
+    const PcmRows &io = pre.stride ? pre : out;
+    if (N < 1 || N > FRAME || !io.p || io.off < 0 || io.off + N > io.stride) { set_err("conceal: a synthesis step outside its rows"); return -1; }
+    if (glue(launch_conceal_gather_rows(idx, n, feat ? b->d_feat : nullptr, feat, feat_stride, pre.p ? b->d_pcm : nullptr,
+                                        pre.p ? pre.p + pre.off : nullptr, pre.stride, N, b->stream),
+             "gather"))
+      return -1;
+    if (st.op == CO_TAIL ? tail_first_device(b, n, b->d_pcm, N, pre.p ? N : 0, M.work)
+                         : synth_first_device(b, n, b->d_feat, b->d_pcm, N, pre.p ? N : 0, M.work))
+      return -1;
+    if (out.p && glue(launch_conceal_scatter_rows(idx, n, b->d_pcm, out.p + out.off, out.stride, N, b->stream), "scatter")) return -1;
   }
   if (commit && launch_state_copy(b->d_state, M.work, idx, nullptr, n, b->stream)) { set_err("conceal: state scatter failed"); return -1; }
   return 0;
@@ -237,11 +275,33 @@ int run_group(LPCNetBatch *b, ConcealMachine &M, const ConcealStep &st, const in
   const ConcealData &d = M.d;
   hipStream_t q = b->stream;
   switch (st.op) {
-  case CO_DC_REMOVE: return glue(launch_conceal_dc(d, idx, n, d_pcm, CONCEAL_DC_REMOVE, q), "DC");
-  case CO_DC_RESTORE: return glue(launch_conceal_dc(d, idx, n, d_pcm, CONCEAL_DC_RESTORE, q), "DC");
-  case CO_DC_CONCEAL: return glue(launch_conceal_dc(d, idx, n, d_pcm, CONCEAL_DC_CONCEAL, q), "DC");
+  case CO_DC_REMOVE: return glue(launch_conceal_dc(d, idx, n, d_pcm, st.a == CDC_CAUSAL ? CONCEAL_DC_REMOVE : CONCEAL_DC_REMOVE_BAK, q), "DC");
+  case CO_DC_RESTORE:
+    if (st.a != CDC_CAUSAL) return glue(launch_conceal_dc_restore_delayed(d, idx, n, d_pcm, q), "DC");
+    return glue(launch_conceal_dc(d, idx, n, d_pcm, CONCEAL_DC_RESTORE, q), "DC");
+  case CO_DC_CONCEAL:
+    return glue(launch_conceal_dc(d, idx, n, d_pcm,
+                                  st.a == CDC_CAUSAL ? CONCEAL_DC_CONCEAL : st.a == CDC_FIRST_LOSS ? CONCEAL_DC_CONCEAL_HALF : CONCEAL_DC_CONCEAL_WHOLE,
+                                  q),
+                "DC");
+  case CO_DC_REDO: return glue(launch_conceal_dc(d, idx, n, d_pcm, CONCEAL_DC_REDO, q), "DC");
   case CO_BURG: return burg_launch(b, d_pcm, nullptr, d.rows, PLC_IN, BURG_FILL_FLAG | (st.a ? BURG_FILL_ZERO : 0), 1.f, mask);
-  case CO_ANALYSIS: return feat_launch(b, d_pcm, nullptr, d.rows + BURG_N, NF, mask, PLC_IN);
+  case CO_ANALYSIS:
+    if (st.a == CA_BUF) { /* the extractor reads dense [B][FRAME] rows */
+      if (glue(launch_conceal_export(d, idx, n, d.frame, 0, 0, FRAME, q), "export")) return -1;
+      return feat_launch(b, d.frame, nullptr, d.rows + BURG_N, NF, mask, PLC_IN);
+    }
+    return feat_launch(b, d_pcm, nullptr, d.rows + BURG_N, NF, mask, PLC_IN);
+  case CO_SYN_SAVE:
+    if (!M.spec || launch_state_copy(M.spec, b->d_state, idx, idx, n, q)) { set_err("conceal: state save failed"); return -1; }
+    return 0;
+  case CO_SYN_RESTORE:
+    if (!M.spec || launch_state_copy(b->d_state, M.spec, idx, idx, n, q)) { set_err("conceal: state restore failed"); return -1; }
+    return 0;
+  case CO_REVERSE: return glue(launch_conceal_reverse(d, idx, n, d_pcm, q), "reverse");
+  case CO_BLEND_BACK: return glue(launch_conceal_blend_back(d, idx, n, q), "blend");
+  case CO_QUEUE_FILL: return glue(launch_conceal_queue_fill(d, idx, n, d_pcm, q), "queue fill");
+  case CO_REORDER: return glue(launch_conceal_reorder(d, idx, n, d_pcm, q), "reorder");
   case CO_PREDICT:
     return plc_launch(b, st.a == CP_ZERO ? nullptr : d.rows, st.a == CP_ROW_DISCARD ? nullptr : d.features, mask);
   case CO_PLC_PUSH: return glue(launch_conceal_plc_push(d, idx, n, q), "plc_copy");
@@ -260,6 +320,8 @@ int run_group(LPCNetBatch *b, ConcealMachine &M, const ConcealStep &st, const in
     case CM_APPEND: return glue(launch_conceal_move(d, idx, n, d_pcm, st.b, 0, 0, FRAME, q), "move");
     case CM_NEWEST: return glue(launch_conceal_move(d, idx, n, d_pcm, d.buf, 0, 0, FRAME, q), "move");
     case CM_SHIFT: return glue(launch_conceal_move(d, idx, n, nullptr, 0, 1, FRAME, d.buf, q), "move");
+    case CM_HEAD_OUT: return glue(launch_conceal_export(d, idx, n, d_pcm, 0, FRAME / 2, FRAME / 2, q), "move");
+    case CM_HEAD_IN: return glue(launch_conceal_move(d, idx, n, d_pcm, FRAME / 2, 0, 0, FRAME / 2, q), "move");
     }
   }
   set_err("conceal: unknown step");
@@ -323,13 +385,17 @@ int conceal_reset_streams(LPCNetBatch *b, int stream)
   if (!M) return 0;
   const ConcealData &d = M->d;
   const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? (size_t)b->B : 1;
-  const std::vector<StateRows> rows = {{d.features, NF * 4},
-                                       {d.pcm, (size_t)(d.buf + FRAME) * 2},
-                                       {d.dc, 16},
-                                       {d.copy, (size_t)(d.delay + 1) * d.nt * 4},
-                                       {d.fec, (size_t)CONCEAL_FEC_ROWS * NF * 4},
-                                       {d.defer, (size_t)CONCEAL_DEFER * NF * 4},
-                                       {d.delta, 4}};
+  std::vector<StateRows> rows = {{d.features, NF * 4},
+                                 {d.pcm, (size_t)(d.buf + FRAME) * 2},
+                                 {d.dc, 16},
+                                 {d.copy, (size_t)(d.delay + 1) * d.nt * 4},
+                                 {d.fec, (size_t)CONCEAL_FEC_ROWS * NF * 4},
+                                 {d.defer, (size_t)CONCEAL_DEFER * NF * 4},
+                                 {d.delta, 4}};
+  if (d.queued) { /* the non-causal mode: queued_samples, dc_buf */
+    rows.push_back({d.queued, FRAME * 2});
+    rows.push_back({d.dc_buf, FRAME / 2 * 2});
+  }
   if (rows_zero(rows, stream, b->B, b->stream)) return -1;
   for (size_t s = first; s < first + n; s++) M->ctrl[s] = conceal_ctrl_reset(d.delay);
   return 0;
@@ -342,8 +408,13 @@ extern "C" {
 LPCNET_EXPORT int lpcnet_batch_conceal_open(LPCNetBatch *b, int options)
 {
   if (plc_ready(b)) return -1;
-  if ((options & ~7) || (options & 3) == 3) { set_err("conceal: options must be LPCNET_CONCEAL_CAUSAL or _CODEC, with or without _DC_FILTER"); return -1; }
-  if ((options & 3) == CONCEAL_OPT_NONCAUSAL) { set_err("conceal: the non-causal mode (LPCNET_PLC_NONCAUSAL) is not supported"); return -1; }
+  if ((options & ~7) || (options & 3) == 3) { set_err("conceal: options must be LPCNET_CONCEAL_CAUSAL, _NONCAUSAL or _CODEC, with or without _DC_FILTER"); return -1; }
+  const bool noncausal = (options & 3) == CONCEAL_OPT_NONCAUSAL;
+  if (noncausal && b->mc.delay != 0) { /* the reference exits (:357-361) */
+    set_err("conceal: the non-causal mode (LPCNET_PLC_NONCAUSAL) needs a model with FEATURES_DELAY 0 "
+            "(lpcnet_batch_set_model_constants or the blob's record); this batch has " + std::to_string(b->mc.delay));
+    return -1;
+  }
   if (b->conceal) { set_err("conceal: a machine is already open on this batch"); return -1; }
   if (b->set_device() || burg_ensure(b)) return -1;
   const size_t B = (size_t)b->B;
@@ -374,6 +445,14 @@ LPCNET_EXPORT int lpcnet_batch_conceal_open(LPCNetBatch *b, int options)
   c.add(w, FRAME / 2);
   c.add(M->work, B);
   c.add(M->io, B * FRAME);
+  if (noncausal) {
+    c.add(M->spec, B);
+    c.add(d.mem_bak, B);
+    c.add(d.queued, B * FRAME);
+    c.add(d.dc_buf, B * (FRAME / 2));
+    c.add(d.rev, B * FRAME);
+    c.add(d.frame, B * FRAME);
+  }
   /* the blend window as the reference computes it per sample (:227), the host's cos */
   float win[FRAME / 2];
   for (int i = 0; i < FRAME / 2; i++) win[i] = (float)(.5 - .5 * cos(M_PI * i / (FRAME / 2)));
@@ -465,11 +544,26 @@ LPCNET_EXPORT int lpcnet_batch_conceal_get_state(LPCNetBatch *b, int stream, int
   const ConcealMachine &M = *b->conceal;
   const ConcealData &d = M.d;
   HIPCHK(hipStreamSynchronize(b->stream));
-  memcpy(ctrl, &M.ctrl[stream], sizeof(ConcealCtrl));
+  memcpy(ctrl, &M.ctrl[stream], CONCEAL_CTRL_INTS * sizeof(int));
   const size_t s = (size_t)stream, np = (size_t)d.buf + FRAME;
   HIPCHK(hipMemcpy(features, d.features + s * NF, NF * 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(pcm_buf, d.pcm + s * np, np * 2, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(dc, d.dc + s * 2, 16, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+LPCNET_EXPORT int lpcnet_batch_conceal_get_state_noncausal(LPCNetBatch *b, int stream, int *queued_update, short *queued_samples, short *dc_buf)
+{
+  if (machine_ready(b)) return -1;
+  if (stream < 0 || stream >= b->B) { set_err("no such stream"); return -1; }
+  const ConcealMachine &M = *b->conceal;
+  if ((M.options & 3) != CONCEAL_OPT_NONCAUSAL) { set_err("conceal: the open machine is not in the non-causal mode"); return -1; }
+  if (b->set_device()) return -1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  const size_t s = (size_t)stream;
+  if (queued_update) *queued_update = M.ctrl[stream].queued_update;
+  if (queued_samples) HIPCHK(hipMemcpy(queued_samples, M.d.queued + s * FRAME, FRAME * 2, hipMemcpyDeviceToHost));
+  if (dc_buf) HIPCHK(hipMemcpy(dc_buf, M.d.dc_buf + s * (FRAME / 2), FRAME / 2 * 2, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -479,6 +573,10 @@ LPCNET_EXPORT int lpcnet_mi355x_conceal_plan(int options, int features_delay, co
 {
   if (nticks < 0 || (nticks > 0 && !lost) || max_steps < 0 || (max_steps > 0 && !steps)) { set_err("bad arguments"); return -1; }
   if (features_delay < 0 || features_delay > CONCEAL_MAX_DELAY) { set_err("conceal plan: FEATURES_DELAY outside 0..4"); return -1; }
+  if ((options & ~7) == 0 && (options & 3) == CONCEAL_OPT_NONCAUSAL && features_delay != 0) {
+    set_err("conceal plan: the non-causal mode needs FEATURES_DELAY 0");
+    return -1;
+  }
   ConcealCtrl c = conceal_ctrl_reset(features_delay);
   std::vector<ConcealStep> all;
   for (int t = 0; t < nticks; t++) {
@@ -487,9 +585,9 @@ LPCNET_EXPORT int lpcnet_mi355x_conceal_plan(int options, int features_delay, co
     if (ev == -2) plan_fec_clear(c);
     else if (ev == -1) (void)plan_fec_add(c, true, store, from, rows);
     for (int k = 0; k < ev; k++) (void)plan_fec_add(c, false, store, from, rows); /* a full buffer drops the add (:118-119) */
-    if (plan_tick(c, lost[t] != 0, options, features_delay, all)) { set_err("conceal plan: options outside the causal and codec modes"); return -1; }
+    if (plan_tick(c, lost[t] != 0, options, features_delay, all)) { set_err("conceal plan: options outside the causal, non-causal and codec modes"); return -1; }
     if (tick_end) tick_end[t] = (int)all.size();
-    if (ctrl) memcpy(ctrl + (size_t)t * CONCEAL_CTRL_INTS, &c, sizeof(c));
+    if (ctrl) memcpy(ctrl + (size_t)t * CONCEAL_CTRL_INTS, &c, CONCEAL_CTRL_INTS * sizeof(int));
   }
   if (!steps) return (int)all.size(); /* the count alone */
   if ((int)all.size() > max_steps) { set_err("conceal plan: more steps than max_steps"); return -1; }

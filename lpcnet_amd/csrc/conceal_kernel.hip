@@ -1,10 +1,12 @@
 /*
  * conceal_kernel.hip -- the glue of lpcnet_plc_update_causal and
- * lpcnet_plc_conceal_causal (lpcnet_plc.c:188-337) between their network and
- * analysis calls, for the streams of an index list: the DC filter, the
- * blend, the attenuation, the st->pcm moves, the plc_copy ring, the FEC row
- * fetch, the deferred-feature push, and the gather / scatter between the
- * streams' rows and the work order a partial-batch synthesis step runs on.
+ * lpcnet_plc_conceal_causal (lpcnet_plc.c:188-337) and of their non-causal
+ * siblings (:339-492) between their network and analysis calls, for the
+ * streams of an index list: the DC filter, the blend, the attenuation, the
+ * st->pcm moves, the plc_copy ring, the FEC row fetch, the deferred-feature
+ * push, the non-causal mode's reversal, backward blend, queue fill and
+ * end-of-tick reorder, and the gather / scatter between the streams' rows and
+ * the work order a partial-batch synthesis step runs on.
  * Elementwise: lane = sample (or feature column), except the two double
  * recursions of the DC filter, lane = stream.  Arithmetic is the reference's
  * expression by expression, with its types; the file is compiled without
@@ -47,15 +49,116 @@ __global__ __launch_bounds__(64) void dc_kernel(ConcealData d, const int *idx, i
     }
   } else if (mode == CONCEAL_DC_RESTORE) { /* :284-286 */
     for (int i = 0; i < FRAME; i++) pcm[i] = (short)(pcm[i] + lp[i]);
-  } else { /* :331-334 */
+  } else if (mode == CONCEAL_DC_CONCEAL) { /* :331-334 */
     const int add = (int)floor(.5 + dc_mem);
     for (int i = 0; i < FRAME; i++) {
       syn_dc += DC_CONST * (pcm[i] - syn_dc);
       pcm[i] = (short)(pcm[i] + add);
     }
+  } else if (mode == CONCEAL_DC_REMOVE_BAK || mode == CONCEAL_DC_REDO) {
+    if (mode == CONCEAL_DC_REMOVE_BAK) { /* :356, :364-366 */
+      d.delta[s] = (int)syn_dc;
+      dc_mem += syn_dc;
+      syn_dc = 0;
+      d.mem_bak[s] = dc_mem;
+    } else { /* :388-393 */
+      const short *syn = d.pcm + (size_t)s * (d.buf + FRAME) + HALF;
+      for (int i = 0; i < FRAME; i++) pcm[i] = (short)(pcm[i] + lp[i]);
+      dc_mem = d.mem_bak[s];
+      for (int i = 0; i < HALF; i++) syn_dc += DC_CONST * (syn[i] - syn_dc);
+      dc_mem += syn_dc;
+      d.delta[s] = (int)((double)d.delta[s] + syn_dc); /* int delta += a double */
+      syn_dc = 0;
+    }
+    for (int i = 0; i < FRAME; i++) { /* :367-371, :394-398 */
+      const short l = (short)(int)floor(.5 + dc_mem);
+      dc_mem += DC_CONST * (pcm[i] - dc_mem);
+      pcm[i] = (short)(pcm[i] - l);
+      lp[i] = l;
+    }
+  } else { /* :480-488 */
+    short *dc_buf = d.dc_buf + (size_t)s * HALF;
+    const int dc = (int)floor(.5 + dc_mem);
+    for (int i = mode == CONCEAL_DC_CONCEAL_HALF ? HALF : 0; i < FRAME; i++) syn_dc += DC_CONST * (pcm[i] - syn_dc);
+    for (int i = 0; i < HALF; i++) {
+      pcm[i] = (short)(pcm[i] + dc_buf[i]);
+      pcm[HALF + i] = (short)(pcm[HALF + i] + dc);
+      dc_buf[i] = (short)dc;
+    }
   }
   d.dc[2 * s] = dc_mem;
   d.dc[2 * s + 1] = syn_dc;
+}
+
+__global__ __launch_bounds__(256) void dc_restore_delayed_kernel(ConcealData d, const int *idx, int n, short *io)
+{
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = g / HALF, i = g % HALF;
+  if (k >= n) return;
+  const int s = idx[k];
+  short *pcm = io + (size_t)s * FRAME;
+  const short *lp = d.lp + (size_t)s * FRAME;
+  short *dc_buf = d.dc_buf + (size_t)s * HALF;
+  pcm[i] = (short)(pcm[i] + dc_buf[i]);        /* :445 */
+  pcm[HALF + i] = (short)(pcm[HALF + i] + lp[i]); /* :446 */
+  dc_buf[i] = lp[HALF + i];                     /* :447 */
+}
+
+__global__ __launch_bounds__(256) void reverse_kernel(ConcealData d, const int *idx, int n, const short *io)
+{
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = g / FRAME, i = g % FRAME;
+  if (k >= n) return;
+  const int s = idx[k];
+  d.rev[(size_t)s * FRAME + i] = io[(size_t)s * FRAME + FRAME - i - 1];
+}
+
+__global__ __launch_bounds__(256) void blend_back_kernel(ConcealData d, const int *idx, int n)
+{
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = g / HALF, i = g % HALF;
+  if (k >= n) return;
+  const int s = idx[k];
+  short *p = d.pcm + (size_t)s * (d.buf + FRAME) + (FRAME - 1 - i);
+  const float w = d.blend_w[i];
+  /* st->pcm[159-i] = (int)floor(.5 + w*st->pcm[159-i] + (1-w)*(rev[i]+delta)): float products, double sums */
+  const float a = w * (float)*p;
+  const float c = (1.f - w) * (float)(d.rev[(size_t)s * FRAME + i] + d.delta[s]);
+  *p = (short)(int)floor((.5 + (double)a) + (double)c);
+}
+
+__global__ __launch_bounds__(256) void queue_fill_kernel(ConcealData d, const int *idx, int n, const short *io)
+{
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const int k = g / FRAME, i = g % FRAME;
+  if (k >= n) return;
+  const int s = idx[k];
+  d.queued[(size_t)s * FRAME + i] = i < HALF ? d.pcm[(size_t)s * (d.buf + FRAME) + HALF + i] : io[(size_t)s * FRAME + i - HALF];
+}
+
+__global__ __launch_bounds__(256) void reorder_kernel(ConcealData d, const int *idx, int n, short *io)
+{
+  const int k = blockIdx.x, i = threadIdx.x;
+  if (k >= n) return;
+  const int s = idx[k];
+  short *pcm = io + (size_t)s * FRAME;
+  short *buf = d.pcm + (size_t)s * (d.buf + FRAME);
+  const short in = i < FRAME ? pcm[i] : (short)0;      /* pcm_save: pcm stands unchanged since :373 / :399 */
+  const short syn = i < HALF ? buf[HALF + i] : (short)0;
+  __syncthreads(); /* every load before any store */
+  if (i < HALF) {
+    pcm[HALF + i] = in; /* :440 */
+    pcm[i] = syn;       /* :441 */
+  }
+  if (i < FRAME) buf[i] = in; /* :442 */
+}
+
+__global__ __launch_bounds__(256) void export_kernel(ConcealData d, const int *idx, int n, short *dst, int dst_off, int src_off, int cnt)
+{
+  const int k = blockIdx.x, i = threadIdx.x;
+  if (k >= n || i >= cnt) return;
+  const int s = idx[k];
+  dst[(size_t)s * FRAME + dst_off + i] = d.pcm[(size_t)s * (d.buf + FRAME) + src_off + i];
 }
 
 __global__ __launch_bounds__(256) void blend_kernel(ConcealData d, const int *idx, int n, short *io)
@@ -160,28 +263,21 @@ __global__ __launch_bounds__(256) void defer_push_kernel(ConcealData d, const in
   }
 }
 
-__global__ __launch_bounds__(256) void gather_kernel(ConcealData d, const int *idx, int n, float *w_feat, int defer_row, short *w_pcm,
-                                                     const short *io, int src_buf, int src_off, int N)
+__global__ __launch_bounds__(256) void gather_kernel(const int *idx, int n, float *w_feat, const float *feat, int feat_stride, short *w_pcm,
+                                                     const short *pcm, int pcm_stride, int N)
 {
   const int k = blockIdx.x;
   if (k >= n) return;
   const int s = idx[k], t = threadIdx.x;
-  if (w_feat && t < NF)
-    w_feat[(size_t)k * NF + t] = defer_row < 0 ? d.features[(size_t)s * NF + t] : d.defer[((size_t)s * CONCEAL_DEFER + defer_row) * NF + t];
-  if (w_pcm && t < N) {
-    const short *src = (src_buf ? d.pcm + (size_t)s * (d.buf + FRAME) : io + (size_t)s * FRAME) + src_off;
-    w_pcm[(size_t)k * N + t] = src[t];
-  }
+  if (w_feat && t < NF) w_feat[(size_t)k * NF + t] = feat[(size_t)s * feat_stride + t];
+  if (w_pcm && t < N) w_pcm[(size_t)k * N + t] = pcm[(size_t)s * pcm_stride + t];
 }
 
-__global__ __launch_bounds__(256) void scatter_kernel(ConcealData d, const int *idx, int n, const short *w_pcm, short *io, int dst_off,
-                                                      int N)
+__global__ __launch_bounds__(256) void scatter_kernel(const int *idx, int n, const short *w_pcm, short *dst, int dst_stride, int N)
 {
   const int k = blockIdx.x, t = threadIdx.x;
   if (k >= n || t >= N) return;
-  const int s = idx[k];
-  short *dst = io ? io + (size_t)s * FRAME + dst_off : d.tmp + (size_t)s * HALF;
-  dst[t] = w_pcm[(size_t)k * N + t];
+  dst[(size_t)idx[k] * dst_stride + t] = w_pcm[(size_t)k * N + t];
 }
 
 __global__ __launch_bounds__(256) void reset_signal_kernel(StreamState *st, const int *idx, int n, int ulaw0)
@@ -232,7 +328,8 @@ int blocks(size_t lanes, int threads) { return (int)((lanes + threads - 1) / thr
 int launch_conceal_dc(const ConcealData &d, const int *idx, int n, short *io, int mode, void *stream)
 {
   if (n <= 0) return 0;
-  if (!idx || !io || mode < CONCEAL_DC_REMOVE || mode > CONCEAL_DC_CONCEAL) return -1;
+  if (!idx || !io || mode < CONCEAL_DC_REMOVE || mode > CONCEAL_DC_CONCEAL_WHOLE) return -1;
+  if (mode > CONCEAL_DC_CONCEAL && (!d.mem_bak || !d.dc_buf)) return -1;
   hipLaunchKernelGGL(dc_kernel, dim3(blocks(n, 64)), dim3(64), 0, (hipStream_t)stream, d, idx, n, io, mode);
   return launched();
 }
@@ -298,23 +395,69 @@ int launch_conceal_defer_push(const ConcealData &d, const int *idx, int n, int a
   return launched();
 }
 
-int launch_conceal_gather(const ConcealData &d, const int *idx, int n, float *w_feat, int defer_row, short *w_pcm, const short *io,
-                          int src_buf, int src_off, int N, void *stream)
+int launch_conceal_gather_rows(const int *idx, int n, float *w_feat, const float *feat, int feat_stride, short *w_pcm, const short *pcm,
+                               int pcm_stride, int N, void *stream)
 {
   if (n <= 0 || (!w_feat && !w_pcm)) return 0;
-  if (!idx || defer_row >= CONCEAL_DEFER) return -1;
-  if (w_pcm && (N < 1 || N > FRAME || src_off < 0 || src_off + N > (src_buf ? d.buf + FRAME : FRAME) || (!src_buf && !io))) return -1;
-  hipLaunchKernelGGL(gather_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, d, idx, n, w_feat, defer_row, w_pcm, io, src_buf,
-                     src_off, N);
+  if (!idx || (w_feat && (!feat || feat_stride < NF)) || (w_pcm && (!pcm || N < 1 || N > FRAME || pcm_stride < N))) return -1;
+  hipLaunchKernelGGL(gather_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, idx, n, w_feat, feat, feat_stride, w_pcm, pcm, pcm_stride,
+                     N);
   return launched();
 }
 
-int launch_conceal_scatter(const ConcealData &d, const int *idx, int n, const short *w_pcm, short *io, int dst_off, int N,
-                           void *stream)
+int launch_conceal_scatter_rows(const int *idx, int n, const short *w_pcm, short *dst, int dst_stride, int N, void *stream)
 {
   if (n <= 0) return 0;
-  if (!idx || !w_pcm || N < 1 || dst_off < 0 || dst_off + N > (io ? FRAME : HALF)) return -1;
-  hipLaunchKernelGGL(scatter_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, d, idx, n, w_pcm, io, dst_off, N);
+  if (!idx || !w_pcm || !dst || N < 1 || N > FRAME || dst_stride < N) return -1;
+  hipLaunchKernelGGL(scatter_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, idx, n, w_pcm, dst, dst_stride, N);
+  return launched();
+}
+
+int launch_conceal_dc_restore_delayed(const ConcealData &d, const int *idx, int n, short *io, void *stream)
+{
+  if (n <= 0) return 0;
+  if (!idx || !io || !d.dc_buf) return -1;
+  hipLaunchKernelGGL(dc_restore_delayed_kernel, dim3(blocks((size_t)n * HALF, 256)), dim3(256), 0, (hipStream_t)stream, d, idx, n, io);
+  return launched();
+}
+
+int launch_conceal_reverse(const ConcealData &d, const int *idx, int n, const short *io, void *stream)
+{
+  if (n <= 0) return 0;
+  if (!idx || !io || !d.rev) return -1;
+  hipLaunchKernelGGL(reverse_kernel, dim3(blocks((size_t)n * FRAME, 256)), dim3(256), 0, (hipStream_t)stream, d, idx, n, io);
+  return launched();
+}
+
+int launch_conceal_blend_back(const ConcealData &d, const int *idx, int n, void *stream)
+{
+  if (n <= 0) return 0;
+  if (!idx || !d.rev || d.buf < 0) return -1;
+  hipLaunchKernelGGL(blend_back_kernel, dim3(blocks((size_t)n * HALF, 256)), dim3(256), 0, (hipStream_t)stream, d, idx, n);
+  return launched();
+}
+
+int launch_conceal_queue_fill(const ConcealData &d, const int *idx, int n, const short *io, void *stream)
+{
+  if (n <= 0) return 0;
+  if (!idx || !io || !d.queued) return -1;
+  hipLaunchKernelGGL(queue_fill_kernel, dim3(blocks((size_t)n * FRAME, 256)), dim3(256), 0, (hipStream_t)stream, d, idx, n, io);
+  return launched();
+}
+
+int launch_conceal_reorder(const ConcealData &d, const int *idx, int n, short *io, void *stream)
+{
+  if (n <= 0) return 0;
+  if (!idx || !io) return -1;
+  hipLaunchKernelGGL(reorder_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, d, idx, n, io);
+  return launched();
+}
+
+int launch_conceal_export(const ConcealData &d, const int *idx, int n, short *dst, int dst_off, int src_off, int cnt, void *stream)
+{
+  if (n <= 0) return 0;
+  if (!idx || !dst || cnt < 1 || cnt > 256 || dst_off < 0 || dst_off + cnt > FRAME || src_off < 0 || src_off + cnt > d.buf + FRAME) return -1;
+  hipLaunchKernelGGL(export_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, d, idx, n, dst, dst_off, src_off, cnt);
   return launched();
 }
 

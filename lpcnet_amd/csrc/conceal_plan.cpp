@@ -1,7 +1,9 @@
 /*
  * conceal_plan.cpp -- lpcnet_plc_update_causal / lpcnet_plc_conceal_causal
- * (lpcnet_plc.c:188-337, PLC_SKIP_UPDATES defined) as a planner over the
- * control state: see conceal_plan.h.  Host only, system compiler.
+ * (lpcnet_plc.c:188-337) and lpcnet_plc_update_non_causal /
+ * lpcnet_plc_conceal_non_causal (:339-492), PLC_SKIP_UPDATES defined, as a
+ * planner over the control state: see conceal_plan.h.  Host only, system
+ * compiler.
  */
 #include "conceal_plan.h"
 
@@ -17,9 +19,16 @@ ConcealCtrl conceal_ctrl_reset(int features_delay)
   return c;
 }
 
-bool conceal_ctrl_ok(const ConcealCtrl &c, int D)
+bool conceal_ctrl_ok(const ConcealCtrl &c, int D, int options)
 {
   const int buf = conceal_buf_size(D);
+  if ((options & 3) == CONCEAL_OPT_NONCAUSAL) {
+    /* a queued update is set by a received tick and consumed by the next tick's first step */
+    if (D != 0 || c.pcm_fill != buf || c.skip_analysis || c.blend || c.feature_buffer_fill || c.fec_read_pos || c.fec_keep_pos) return false;
+    if (c.queued_update != 0 && !(c.queued_update == 1 && c.loss_count == 0)) return false;
+  } else if (c.queued_update) {
+    return false;
+  }
   const bool fill_ok = c.pcm_fill == 0 || (c.pcm_fill >= CONCEAL_HALF && c.pcm_fill <= buf && (c.pcm_fill - CONCEAL_HALF) % CONCEAL_FRAME == 0);
   return fill_ok && c.skip_analysis >= 0 && (c.blend == 0 || c.blend == 1) && c.loss_count >= 0 && c.fec_skip >= 0 &&
          0 <= c.fec_keep_pos && c.fec_keep_pos <= c.fec_read_pos && c.fec_read_pos <= c.fec_fill_pos &&
@@ -133,6 +142,68 @@ struct Plan {
     c.blend = 1;
     if (dc) step(CO_DC_CONCEAL); /* :330-335 */
   }
+
+  /* process_queued_update (:342-347) */
+  void queued()
+  {
+    if (c.queued_update) step(CO_IMPL, CONCEAL_FRAME, CI_QUEUE);
+    c.queued_update = 0;
+  }
+
+  /* lpcnet_plc_update_non_causal (:349-450).  pcm_save (:373, :399) is the
+   * caller's pcm as it stands until :440, so it takes no step of its own:
+   * CO_REORDER reads pcm before it writes. */
+  void update_noncausal()
+  {
+    queued();                                /* :362 */
+    if (dc) step(CO_DC_REMOVE, CDC_NONCAUSAL); /* :363-372 */
+    step(CO_BURG, c.loss_count > 0 ? 1 : 0); /* :375; its row with zero features at :380-382 */
+    if (c.loss_count > 0) {
+      step(CO_PREDICT, CP_BURG_ONLY);             /* :383 */
+      step(CO_SYN_SAVE);                          /* :384 */
+      step(CO_IMPL, CONCEAL_HALF, CI_BUF_OUT);    /* :385 */
+      if (dc) step(CO_DC_REDO);                   /* :387-400 */
+      step(CO_REVERSE);                           /* :403 */
+      step(CO_RESET_SIGNAL);                      /* :404 */
+      step(CO_IMPL, CONCEAL_FRAME, CI_REV);       /* :405 */
+      step(CO_TAIL, CONCEAL_HALF, CT_REV);        /* :406 */
+      step(CO_BLEND_BACK);                        /* :407-411 */
+      step(CO_SYN_RESTORE);                       /* :414 */
+      step(CO_QUEUE_FILL);                        /* :416-418 */
+      c.queued_update = 1;
+      step(CO_ANALYSIS, CA_BUF);                  /* :423-426 */
+    }
+    step(CO_ANALYSIS, CA_PCM); /* :429-432 */
+    if (c.loss_count == 0) {
+      step(CO_PREDICT, CP_FULL);                  /* :434-436 */
+      step(CO_IMPL, CONCEAL_HALF, CI_ANALYSED);   /* :437 */
+      step(CO_TAIL, CONCEAL_HALF, CT_PCM_PRE);    /* :438 */
+    }
+    step(CO_REORDER); /* :440-442 */
+    c.loss_count = 0;
+    if (dc) step(CO_DC_RESTORE, CDC_NONCAUSAL); /* :444-448 */
+  }
+
+  /* lpcnet_plc_conceal_non_causal (:452-492) */
+  void conceal_noncausal()
+  {
+    queued();                            /* :456 */
+    step(CO_PREDICT, CP_ZERO);           /* :459 */
+    step(CO_ATTENUATE, c.loss_count);    /* :460-461: loss_count counts up at the end (:490) */
+    if (c.loss_count == 0) {
+      step(CO_PCM_MOVE, CM_HEAD_OUT);           /* :464 */
+      step(CO_IMPL, CONCEAL_HALF, CI_BUF_HI);   /* :465 */
+      step(CO_TAIL, CONCEAL_HALF, CT_PCM_HI);   /* :466 */
+    } else {
+      step(CO_IMPL, CONCEAL_HALF, CI_PCM_LO);   /* :468 */
+      step(CO_TAIL, CONCEAL_HALF, CT_PCM_HI);   /* :469 */
+      step(CO_PCM_MOVE, CM_HEAD_IN);            /* :471 */
+      step(CO_ANALYSIS, CA_BUF);                /* :472-475 */
+    }
+    step(CO_PCM_MOVE, CM_TAIL_HALF); /* :477 */
+    if (dc) step(CO_DC_CONCEAL, c.loss_count == 0 ? CDC_FIRST_LOSS : CDC_NONCAUSAL); /* :479-489 */
+    c.loss_count++;
+  }
 };
 
 }  // namespace
@@ -140,11 +211,18 @@ struct Plan {
 int plan_tick(ConcealCtrl &c, bool lost, int options, int features_delay, std::vector<ConcealStep> &out)
 {
   const int mode = options & 3;
-  if ((options & ~7) || (mode != CONCEAL_OPT_CAUSAL && mode != CONCEAL_OPT_CODEC)) return -1;
+  if ((options & ~7) || mode == 3) return -1;
   if (features_delay < 0 || features_delay > CONCEAL_MAX_DELAY) return -1;
-  Plan p{c, features_delay, mode == CONCEAL_OPT_CAUSAL, (options & CONCEAL_OPT_DC_FILTER) != 0, {}};
-  if (lost) p.conceal();
-  else p.update();
+  if (mode == CONCEAL_OPT_NONCAUSAL && features_delay != 0) return -1; /* :357-361 */
+  Plan p{c, features_delay, mode != CONCEAL_OPT_CODEC, (options & CONCEAL_OPT_DC_FILTER) != 0, {}};
+  if (mode == CONCEAL_OPT_NONCAUSAL) {
+    if (lost) p.conceal_noncausal();
+    else p.update_noncausal();
+  } else if (lost) {
+    p.conceal();
+  } else {
+    p.update();
+  }
   c = p.c;
   out.insert(out.end(), p.s.begin(), p.s.end());
   return 0;

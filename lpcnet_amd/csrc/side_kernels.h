@@ -284,7 +284,7 @@ __host__ __device__ inline int enc_main_pitch(const float *thr, float cp)
 /* The data side of lpcnet_plc_update / lpcnet_plc_conceal between their
  * network and analysis calls (conceal_kernel.hip): per stream, beside
  * StreamState (the synthesis snapshots keep their size), what of
- * LPCNetPLCState (lpcnet_private.h:78-106) the causal modes carry, and the
+ * LPCNetPLCState (lpcnet_private.h:78-106) the three modes carry, and the
  * scratch a tick hands over through.  Every launcher takes the streams it
  * works on as an index list idx [n] in device memory; a stream appears in a
  * list at most once. */
@@ -308,10 +308,38 @@ struct ConcealData {
   int *delta;         /* [B] its delta; zero without the DC filter */
   short *tmp;         /* [B][FRAME / 2] the speculative half frame */
   const float *blend_w; /* [FRAME / 2] (float)(.5 - .5*cos(M_PI*i/80)), the host's cos */
+  /* the non-causal mode (lpcnet_plc.c:339-492), null in the others: state */
+  short *queued;      /* [B][FRAME] queued_samples */
+  short *dc_buf;      /* [B][FRAME / 2] */
+  /* and scratch of one tick */
+  short *rev;         /* [B][FRAME] lpcnet_plc_update_non_causal's rev */
+  double *mem_bak;    /* [B] its mem_bak */
+  short *frame;       /* [B][FRAME] st->pcm[0 .. 160) as dense rows, for the analysis launch */
 };
-enum { CONCEAL_DC_REMOVE = 0, CONCEAL_DC_RESTORE = 1, CONCEAL_DC_CONCEAL = 2 };
-/* the DC filter on io [B][FRAME] (lpcnet_plc.c:195-204, 283-287, 330-335): one lane per stream */
+enum {
+  CONCEAL_DC_REMOVE = 0,
+  CONCEAL_DC_RESTORE = 1,
+  CONCEAL_DC_CONCEAL = 2,
+  /* the non-causal forms */
+  CONCEAL_DC_REMOVE_BAK = 3,    /* :364-372: CONCEAL_DC_REMOVE that keeps mem_bak */
+  CONCEAL_DC_REDO = 4,          /* :388-398 */
+  CONCEAL_DC_CONCEAL_HALF = 5,  /* :480-488, syn_dc over pcm[80 .. 160) (:482) */
+  CONCEAL_DC_CONCEAL_WHOLE = 6  /* :480-488, syn_dc over pcm[0 .. 160) (:484) */
+};
+/* the DC filter on io [B][FRAME] (lpcnet_plc.c:195-204, 283-287, 330-335; 363-372, 387-398, 479-489): one lane per stream */
 int launch_conceal_dc(const ConcealData &d, const int *idx, int n, short *io, int mode, void *stream);
+/* io[0 .. 80) += dc_buf, io[80 .. 160) += lp[0 .. 80), dc_buf = lp[80 .. 160) (:444-448) */
+int launch_conceal_dc_restore_delayed(const ConcealData &d, const int *idx, int n, short *io, void *stream);
+/* rev[i] = io[159 - i] (:403) */
+int launch_conceal_reverse(const ConcealData &d, const int *idx, int n, const short *io, void *stream);
+/* st->pcm[159 - i] = blend of itself and rev[i] + delta, i < 80 (:407-411) */
+int launch_conceal_blend_back(const ConcealData &d, const int *idx, int n, void *stream);
+/* queued_samples = st->pcm[80 .. 160), io[0 .. 80) (:417-418) */
+int launch_conceal_queue_fill(const ConcealData &d, const int *idx, int n, const short *io, void *stream);
+/* io[80 .. 160) = io[0 .. 80), io[0 .. 80) = st->pcm[80 .. 160), st->pcm[0 .. 160) = io as it was (:440-442) */
+int launch_conceal_reorder(const ConcealData &d, const int *idx, int n, short *io, void *stream);
+/* rows [B][FRAME] at dst_off = st->pcm[src_off .. + cnt): dst the io rows (:464) or d.frame */
+int launch_conceal_export(const ConcealData &d, const int *idx, int n, short *dst, int dst_off, int src_off, int cnt, void *stream);
 /* io[0 .. 80) = blend of io and tmp - delta (:225-229) */
 int launch_conceal_blend(const ConcealData &d, const int *idx, int n, short *io, void *stream);
 /* features[0] = MAX16(-10, features[0] + att_table[.]) (:318-319) */
@@ -326,14 +354,13 @@ int launch_conceal_plc_restore(const ConcealData &d, const int *idx, int n, int 
 int launch_conceal_fec_fetch(const ConcealData &d, const int *idx, int n, int pos, void *stream);
 /* run_frame_network_deferred's buffer push: analysed ? rows[36 .. 56) : features, `fill` frames held before */
 int launch_conceal_defer_push(const ConcealData &d, const int *idx, int n, int analysed, int fill, void *stream);
-/* work order [n][NF] / [n][N] from the streams' rows: w_feat (null: none) from
- * features (defer_row < 0) or the deferred buffer's row; w_pcm (null: none)
- * from st->pcm (src_buf) or the io row, at src_off */
-int launch_conceal_gather(const ConcealData &d, const int *idx, int n, float *w_feat, int defer_row, short *w_pcm, const short *io,
-                          int src_buf, int src_off, int N, void *stream);
-/* w_pcm [n][N] to the io rows at dst_off, or to tmp (io null) */
-int launch_conceal_scatter(const ConcealData &d, const int *idx, int n, const short *w_pcm, short *io, int dst_off, int N,
-                           void *stream);
+/* between the streams' rows and the work order [n][NF] / [n][N] a partial-batch
+ * synthesis step runs on: w_feat (null: none) from feat[s * feat_stride ..),
+ * w_pcm (null: none) from pcm[s * pcm_stride ..); the work order's w_pcm to
+ * dst[s * dst_stride ..).  The callers bound the rows. */
+int launch_conceal_gather_rows(const int *idx, int n, float *w_feat, const float *feat, int feat_stride, short *w_pcm, const short *pcm,
+                               int pcm_stride, int N, void *stream);
+int launch_conceal_scatter_rows(const int *idx, int n, const short *w_pcm, short *dst, int dst_stride, int N, void *stream);
 /* lpcnet_reset_signal (lpcnet.c:226-233) on st[idx[k]]; ulaw0 = lin2ulaw(0.f) */
 int launch_conceal_reset_signal(StreamState *st, const int *idx, int n, int ulaw0, void *stream);
 /* lpcnet_plc_fec_add's RNN_MOVE (:121) and RNN_COPY (:126) on one stream */

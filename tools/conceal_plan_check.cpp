@@ -23,6 +23,22 @@
  *   - arguments outside the supported modes are refused with the control
  *     state and the step list untouched; a full FEC queue refuses an add.
  *
+ * The same 1,024 patterns in the non-causal mode, with and without the DC
+ * filter, at FEATURES_DELAY 0 (the only delay the mode has; 1..4 are refused)
+ * and under the three FEC schedules:
+ *
+ *   - only loss_count and queued_update leave their reset values, and the FEC
+ *     events move the queue's fill side alone (conceal_ctrl_ok);
+ *   - a received tick after a received one is one impl of 80 and one tail of
+ *     80, both teacher-forced; the speculative steps (save, reverse, clear,
+ *     impl 160, tail, blend, restore, queue fill) appear together, in that
+ *     order, exactly in a received tick that follows a lost one, and the next
+ *     tick starts with the queued impl of 160;
+ *   - loss_count counts the lost ticks since the last received one, and the
+ *     attenuation sees it before the increment;
+ *   - no step of the causal modes' own (plc_copy, FEC fetch, deferred push,
+ *     flush, rewind, discard) appears.
+ *
  * Then the merge of a batch's tick (merge_tick): streams on pseudo-random
  * loss patterns, so that many control states meet in one tick, merged tick by
  * tick.  Every class's launching steps appear in its own order, each exactly
@@ -110,6 +126,60 @@ static void check_step(const ConcealStep &s, bool lost, bool all_received, int D
   if (all_received) CHECK(s.op != CO_IMPL && s.op != CO_TAIL && s.op != CO_FLUSH, "pattern %#x: synthesis step %d without a loss", pattern, s.op);
 }
 
+static bool k_first_is_queue(const std::vector<ConcealStep> &s)
+{
+  return !s.empty() && s[0].op == CO_IMPL && s[0].a == CONCEAL_FRAME && s[0].b == CI_QUEUE;
+}
+
+/* one tick of the non-causal mode (lpcnet_plc.c:342-492) */
+static void check_noncausal_tick(const std::vector<ConcealStep> &s, bool lost, bool prev_lost, bool queued_before, int loss_before, bool dc,
+                                 unsigned pattern)
+{
+  std::vector<int> spec;
+  int impl80 = 0, tail80 = 0, impl160 = 0, analyses = 0;
+  for (size_t k = 0; k < s.size(); k++) {
+    const ConcealStep &x = s[k];
+    switch (x.op) {
+    case CO_DC_REMOVE:
+    case CO_DC_RESTORE: CHECK(dc && !lost && x.a == CDC_NONCAUSAL, "pattern %#x: DC step %d form %d", pattern, x.op, x.a); break;
+    case CO_DC_REDO: CHECK(dc && !lost && prev_lost, "pattern %#x: DC redo", pattern); break;
+    case CO_DC_CONCEAL: CHECK(dc && lost && x.a == (loss_before == 0 ? CDC_FIRST_LOSS : CDC_NONCAUSAL), "pattern %#x: DC conceal form %d", pattern, x.a); break;
+    case CO_BURG: CHECK(!lost && x.a == (prev_lost ? 1 : 0), "pattern %#x: burg %d", pattern, x.a); break;
+    case CO_ANALYSIS: CHECK(x.a == CA_PCM || x.a == CA_BUF, "analysis of %d", x.a); analyses++; break;
+    case CO_PREDICT: CHECK(x.a == (lost ? CP_ZERO : prev_lost ? CP_BURG_ONLY : CP_FULL), "pattern %#x: predict %d", pattern, x.a); break;
+    case CO_ATTENUATE: CHECK(lost && x.a == loss_before, "attenuate(%d) at loss_count %d", x.a, loss_before); break;
+    case CO_IMPL:
+      CHECK(x.b >= CI_QUEUE && x.b <= CI_PCM_LO, "impl kind %d", x.b);
+      CHECK(x.a == ((x.b == CI_QUEUE || x.b == CI_REV) ? CONCEAL_FRAME : CONCEAL_HALF), "impl(%d) kind %d", x.a, x.b);
+      if (x.b == CI_QUEUE) CHECK(k == 0 && queued_before, "pattern %#x: the queued update is not the tick's first step", pattern);
+      if (x.a == CONCEAL_FRAME) impl160++;
+      else impl80++;
+      if (x.b == CI_REV) spec.push_back(x.op);
+      break;
+    case CO_TAIL:
+      CHECK(x.a == CONCEAL_HALF && x.b >= CT_REV && x.b <= CT_PCM_HI, "tail(%d) kind %d", x.a, x.b);
+      tail80++;
+      if (x.b == CT_REV) spec.push_back(x.op);
+      break;
+    case CO_PCM_MOVE: CHECK(lost && (x.a == CM_TAIL_HALF || x.a == CM_HEAD_OUT || x.a == CM_HEAD_IN), "move %d", x.a); break;
+    case CO_SYN_SAVE:
+    case CO_REVERSE:
+    case CO_RESET_SIGNAL:
+    case CO_BLEND_BACK:
+    case CO_SYN_RESTORE:
+    case CO_QUEUE_FILL: spec.push_back(x.op); break;
+    case CO_REORDER: CHECK(!lost, "reorder in a lost tick"); break;
+    default: CHECK(false, "pattern %#x: step %d in the non-causal mode", pattern, x.op);
+    }
+  }
+  const std::vector<int> want = {CO_SYN_SAVE, CO_REVERSE, CO_RESET_SIGNAL, CO_IMPL, CO_TAIL, CO_BLEND_BACK, CO_SYN_RESTORE, CO_QUEUE_FILL};
+  CHECK(spec == (!lost && prev_lost ? want : std::vector<int>()), "pattern %#x: the speculative steps", pattern);
+  CHECK((k_first_is_queue(s)) == queued_before, "pattern %#x: a queued update not consumed", pattern);
+  if (!lost && !prev_lost) CHECK(impl80 == 1 && tail80 == 1 && impl160 == (queued_before ? 1 : 0) && analyses == 1, "pattern %#x: a received tick", pattern);
+  if (!lost && prev_lost) CHECK(impl80 == 1 && tail80 == 1 && impl160 == 1 && analyses == 2, "pattern %#x: the first received tick", pattern);
+  if (lost) CHECK(impl80 == 1 && tail80 == 1 && analyses == (loss_before ? 1 : 0), "pattern %#x: a lost tick", pattern);
+}
+
 int main()
 {
   long plans = 0, steps = 0;
@@ -135,7 +205,41 @@ int main()
           }
           plans++;
         }
+  /* the non-causal mode */
+  for (int options : {1, 5})
+    for (int f = 0; f < 3; f++)
+      for (unsigned pattern = 0; pattern < (1u << TICKS); pattern++) {
+        ConcealCtrl c = conceal_ctrl_reset(0);
+        bool prev_lost = false;
+        for (int t = 0; t < TICKS; t++) {
+          const bool lost = (pattern >> t) & 1;
+          fec_events(c, f, t);
+          CHECK(conceal_ctrl_ok(c, 0, options), "after the FEC events of tick %d, pattern %#x", t, pattern);
+          const ConcealCtrl before = c;
+          std::vector<ConcealStep> s;
+          CHECK(plan_tick(c, lost, options, 0, s) == 0, "plan_tick refused the non-causal mode at delay 0");
+          CHECK(conceal_ctrl_ok(c, 0, options), "tick %d of pattern %#x, options %d: loss_count %d queued_update %d", t, pattern, options,
+                c.loss_count, c.queued_update);
+          CHECK(c.loss_count == (lost ? before.loss_count + 1 : 0), "loss_count %d after %d", c.loss_count, before.loss_count);
+          CHECK(c.queued_update == (!lost && prev_lost ? 1 : 0), "queued_update %d", c.queued_update);
+          CHECK(c.fec_fill_pos == before.fec_fill_pos && c.fec_skip == before.fec_skip, "a tick moved the FEC queue");
+          check_noncausal_tick(s, lost, before.loss_count > 0, before.queued_update != 0, before.loss_count, (options & CONCEAL_OPT_DC_FILTER) != 0,
+                               pattern);
+          prev_lost = lost;
+          steps += (long)s.size();
+        }
+        plans++;
+      }
   /* refusals leave everything as it was */
+  {
+    for (int D = 1; D <= CONCEAL_MAX_DELAY; D++) {
+      ConcealCtrl c = conceal_ctrl_reset(D);
+      const ConcealCtrl before = c;
+      std::vector<ConcealStep> s;
+      for (int options : {1, 5}) CHECK(plan_tick(c, false, options, D, s) == -1, "the non-causal mode accepted at delay %d", D);
+      CHECK(s.empty() && !memcmp(&c, &before, sizeof(c)), "a refused plan_tick changed its arguments");
+    }
+  }
   {
     ConcealCtrl c = conceal_ctrl_reset(2);
     const ConcealCtrl before = c;
@@ -157,7 +261,8 @@ int main()
   /* the merge of a batch's tick */
   long merged = 0, positional = 0;
   for (int D : {0, 2, 4})
-    for (int options : {0, 2, 4}) {
+    for (int options : {0, 2, 4, 1, 5}) {
+      if ((options & 3) == CONCEAL_OPT_NONCAUSAL && D != 0) continue;
       const int S = 97;
       std::vector<ConcealCtrl> ctrl(S, conceal_ctrl_reset(D));
       unsigned rnd = 12345u + D * 7 + options;
