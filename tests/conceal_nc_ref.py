@@ -22,10 +22,10 @@ import os
 
 import numpy as np
 
-from conceal_ref import (ANALYSIS, ATT_TABLE, ATTENUATE, BURG, CP_BURG_ONLY, CP_FULL, CP_ZERO, CTRL, DC_CONCEAL, DC_CONST,
+from conceal_ref import (ANALYSIS, ATT_TABLE, ATTENUATE, BURG, COUNTERS, CP_BURG_ONLY, CP_FULL, CP_ZERO, CTRL, DC_CONCEAL, DC_CONST,
                          DC_FILTER, DC_REMOVE, DC_RESTORE, FRAME_SIZE, IMPL, NB_BANDS, NB_FEATURES, NONCAUSAL, NTICKS,
                          PCM_MOVE, PLC_MAX_FEC, PREDICT, RESET_SIGNAL, SCRIPTS, SIGNALS, TAIL, TRAINING_OFFSET, CM_TAIL_HALF, F,
-                         _short, fec_events, fec_row, lost_matrix, plc_buf_size, received_pcm)
+                         _short, _wraps, fec_events, fec_row, lost_matrix, plc_buf_size, received_pcm)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conceal_noncausal.npz")
 HALF = TRAINING_OFFSET
@@ -53,6 +53,7 @@ class ConcealNcRef:
         self.buf = plc_buf_size(0)
         self.stub = stub
         self.trace = []
+        self.count = dict.fromkeys(COUNTERS, 0)  # conceal_ref.COUNTERS; the ring and the long moves are not this mode's
         if not stub:
             import burg_ref
             import enc_ref
@@ -140,7 +141,10 @@ class ConcealNcRef:
     def _dc_pass(self, pcm, lp):  # :367-371, :394-398
         for i in range(FRAME_SIZE):
             lp[i] = _short(math.floor(.5 + self.dc_mem))
+            self.count["dc_tie"] += self.dc_mem - math.floor(self.dc_mem) == .5 and math.floor(self.dc_mem) % 2 == 0
             self.dc_mem += DC_CONST * (float(pcm[i]) - self.dc_mem)
+            self.count["l_negative"] += lp[i] < 0
+            self.count["dc_remove_wrap"] += _wraps(int(pcm[i]) - int(lp[i]))
             pcm[i] = _short(int(pcm[i]) - int(lp[i]))
 
     def _attenuate(self):  # :460-461
@@ -150,6 +154,8 @@ class ConcealNcRef:
             v = F(F(f0 + ATT_TABLE[9]) - F(2 * (self.loss_count - 9)))
         else:
             v = F(f0 + ATT_TABLE[self.loss_count])
+        self.count["loss_ge_10"] += self.loss_count >= 10
+        self.count["clamp"] += bool(-10 > v)
         self.features[0] = F(-10) if -10 > v else v
 
     # -- lpcnet_plc_update_non_causal (:349-450) ---------------------------------
@@ -160,6 +166,7 @@ class ConcealNcRef:
         lp = np.zeros(FRAME_SIZE, np.int16)
         mem_bak = 0.0
         delta = int(self.syn_dc)  # :356
+        self.count["delta_trunc"] += delta < 0 and delta != math.floor(self.syn_dc)
         self._process_queued_update()  # :362
         if self.remove_dc:  # :363-372
             self._t(DC_REMOVE, CDC_NONCAUSAL)
@@ -185,6 +192,7 @@ class ConcealNcRef:
             if self.remove_dc:  # :387-400
                 self._t(DC_REDO)
                 for i in range(FRAME_SIZE):
+                    self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + int(lp[i]))
                     pcm[i] = _short(int(pcm[i]) + int(lp[i]))
                 self.dc_mem = mem_bak
                 for i in range(TRAINING_OFFSET):
@@ -210,6 +218,7 @@ class ConcealNcRef:
                     j = FRAME_SIZE - 1 - i
                     a = F(w * F(self.pcm[j]))
                     c = F(F(F(1) - w) * F(int(rev[i]) + delta))
+                    self.count["blend_wrap"] += _wraps(math.floor((.5 + float(a)) + float(c)))
                     self.pcm[j] = _short(math.floor((.5 + float(a)) + float(c)))
             self._t(SYN_RESTORE)  # :414
             if not stub:
@@ -239,8 +248,10 @@ class ConcealNcRef:
         if self.remove_dc:  # :444-448
             self._t(DC_RESTORE, CDC_NONCAUSAL)
             for i in range(TRAINING_OFFSET):
+                self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + int(self.dc_buf[i]))
                 pcm[i] = _short(int(pcm[i]) + int(self.dc_buf[i]))
             for i in range(TRAINING_OFFSET, FRAME_SIZE):
+                self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + int(lp[i - TRAINING_OFFSET]))
                 pcm[i] = _short(int(pcm[i]) + int(lp[i - TRAINING_OFFSET]))
             self.dc_buf[:] = lp[HALF:]
         return pcm
@@ -276,11 +287,14 @@ class ConcealNcRef:
         if self.remove_dc:  # :479-489
             self._t(DC_CONCEAL, CDC_FIRST_LOSS if self.loss_count == 0 else CDC_NONCAUSAL)
             dc = int(math.floor(.5 + self.dc_mem))
+            self.count["l_negative"] += dc < 0
             for i in range(TRAINING_OFFSET if self.loss_count == 0 else 0, FRAME_SIZE):
                 self.syn_dc += DC_CONST * (float(pcm[i]) - self.syn_dc)
             for i in range(TRAINING_OFFSET):
+                self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + int(self.dc_buf[i]))
                 pcm[i] = _short(int(pcm[i]) + int(self.dc_buf[i]))
             for i in range(TRAINING_OFFSET, FRAME_SIZE):
+                self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + dc)
                 pcm[i] = _short(int(pcm[i]) + dc)
             self.dc_buf[:] = _short(dc)
         self.loss_count += 1  # :490

@@ -59,6 +59,24 @@ def _short(v: int) -> int:
     return ((int(v) + 32768) & 0xFFFF) - 32768
 
 
+# What a run went through, counted beside the arithmetic (tests/test_conceal_edge_ref.py reads the aims of
+# tests/conceal_edge.py's cases from them); no counter feeds back into a value.
+COUNTERS = ("dc_remove_wrap",   # pcm - l left int16 before its short store (:202)
+            "dc_add_wrap",      # pcm + lp (:285) or pcm + add (:333) did
+            "l_negative",       # floor(.5 + dc_mem) < 0
+            "delta_trunc",      # delta < 0 and (int)syn_dc != floor(syn_dc)
+            "blend_wrap",       # the blend's integer left int16 before its short store (:228, :411)
+            "clamp",            # MAX16(-10, .) took the -10 (:319)
+            "loss_ge_10",       # the loss_count >= 10 branch of :319
+            "move_max",         # the longest PCM_MOVE, in shorts
+            "restore_at_delay",  # PLC_RESTORE with which == FEATURES_DELAY (:217)
+            "dc_tie")           # floor(.5 + dc_mem) on a dc_mem of an even integer + .5 exactly, where rint goes down
+
+
+def _wraps(v: int) -> bool:
+    return not -32768 <= int(v) <= 32767
+
+
 class ConcealRef:
     """One LPCNetPLCState.  options: CAUSAL or CODEC, with or without
     DC_FILTER; delay: FEATURES_DELAY of the model's build."""
@@ -73,6 +91,7 @@ class ConcealRef:
         self.buf = plc_buf_size(delay)
         self.stub = stub
         self.trace = []
+        self.count = dict.fromkeys(COUNTERS, 0)
         if not stub:
             import burg_ref
             import enc_ref
@@ -172,6 +191,7 @@ class ConcealRef:
 
     def _plc_restore(self, k):
         self._t(PLC_RESTORE, k)
+        self.count["restore_at_delay"] += k == self.delay
         if not self.stub:
             self.net.restore(self.plc_copy[k])
 
@@ -179,8 +199,12 @@ class ConcealRef:
         self._t(ANALYSIS)
         return None if self.stub else self.enc.frame(pcm)[:NB_FEATURES]
 
+    def _moved(self, n):
+        self.count["move_max"] = max(self.count["move_max"], n)
+
     def _shift(self):
         self._t(PCM_MOVE, CM_SHIFT)
+        self._moved(self.buf)
         self.pcm[:self.buf] = self.pcm[FRAME_SIZE:FRAME_SIZE + self.buf].copy()  # RNN_MOVE
 
     # -- lpcnet_plc_update_causal (:188-290) --------------------------------------
@@ -194,10 +218,14 @@ class ConcealRef:
             self._t(DC_REMOVE)
             self.dc_mem += self.syn_dc
             delta = int(self.syn_dc)
+            self.count["delta_trunc"] += delta < 0 and delta != math.floor(self.syn_dc)
             self.syn_dc = 0.0
             for i in range(FRAME_SIZE):
                 lp[i] = _short(math.floor(.5 + self.dc_mem))
+                self.count["dc_tie"] += self.dc_mem - math.floor(self.dc_mem) == .5 and math.floor(self.dc_mem) % 2 == 0
                 self.dc_mem += DC_CONST * (float(pcm[i]) - self.dc_mem)
+                self.count["l_negative"] += lp[i] < 0
+                self.count["dc_remove_wrap"] += _wraps(int(pcm[i]) - int(lp[i]))
                 pcm[i] = _short(int(pcm[i]) - int(lp[i]))
         blend_now = bool(self.skip_analysis and self.blend and self.enable_blending)
         self._t(BURG, 1 if blend_now else 0)
@@ -225,6 +253,7 @@ class ConcealRef:
                             w = F(.5 - .5 * math.cos(math.pi * i / HALF))
                             a = F(w * F(pcm[i]))
                             c = F(F(F(1) - w) * F(int(tmp[i]) - delta))
+                            self.count["blend_wrap"] += _wraps(math.floor((.5 + float(a)) + float(c)))
                             pcm[i] = _short(math.floor((.5 + float(a)) + float(c)))
                     self._t(IMPL, HALF, CI_PCM_PRE)  # :231
                     if not stub:
@@ -238,10 +267,12 @@ class ConcealRef:
                     if not stub:
                         self.lpcnet.reset_signal()
                 self._t(PCM_MOVE, CM_TAIL_HALF)  # :242-243
+                self._moved(TRAINING_OFFSET)
                 self.pcm[:TRAINING_OFFSET] = pcm[HALF:]
                 self.pcm_fill = TRAINING_OFFSET
             else:
                 self._t(PCM_MOVE, CM_APPEND, self.pcm_fill)  # :245-246
+                self._moved(FRAME_SIZE)
                 self.pcm[self.pcm_fill:self.pcm_fill + FRAME_SIZE] = pcm
                 self.pcm_fill += FRAME_SIZE
         enc_features = self._analysis(pcm)  # :251-254
@@ -262,6 +293,7 @@ class ConcealRef:
             self.skip_analysis -= 1
         else:
             self._t(PCM_MOVE, CM_NEWEST)  # :271
+            self._moved(FRAME_SIZE)
             self.pcm[self.buf:] = pcm
             self._deferred(CD_ANALYSED, enc_features)  # :275 (PLC_SKIP_UPDATES)
             self._shift()  # :280
@@ -269,6 +301,7 @@ class ConcealRef:
         if self.remove_dc:  # :283-287
             self._t(DC_RESTORE)
             for i in range(FRAME_SIZE):
+                self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + int(lp[i]))
                 pcm[i] = _short(int(pcm[i]) + int(lp[i]))
         self.blend = 0
         return pcm
@@ -307,6 +340,8 @@ class ConcealRef:
             v = F(F(f0 + ATT_TABLE[9]) - F(2 * (self.loss_count - 9)))
         else:
             v = F(f0 + ATT_TABLE[self.loss_count])
+        self.count["loss_ge_10"] += self.loss_count >= 10
+        self.count["clamp"] += bool(-10 > v)
         self.features[0] = F(-10) if -10 > v else v
         self._t(IMPL, TRAINING_OFFSET, CI_PCM_OUT)  # :320
         if not stub:
@@ -316,8 +351,10 @@ class ConcealRef:
         if self.remove_dc:  # :330-335
             self._t(DC_CONCEAL)
             add = int(math.floor(.5 + self.dc_mem))
+            self.count["l_negative"] += add < 0
             for i in range(FRAME_SIZE):
                 self.syn_dc += DC_CONST * (float(pcm[i]) - self.syn_dc)
+                self.count["dc_add_wrap"] += _wraps(int(pcm[i]) + add)
                 pcm[i] = _short(int(pcm[i]) + add)
         return pcm
 

@@ -40,7 +40,7 @@ def show(steps):
 
 
 @pytest.mark.parametrize("options", [CR.CAUSAL, CR.CODEC], ids=["causal", "codec"])
-@pytest.mark.parametrize("delay", [0, 2])
+@pytest.mark.parametrize("delay", [0, 1, 2, 3, 4])
 def test_every_pattern_of_ten_ticks(options, delay):
     for pattern in range(1 << TICKS):
         lost = [(pattern >> t) & 1 for t in range(TICKS)]
@@ -52,7 +52,7 @@ def test_every_pattern_of_ten_ticks(options, delay):
 
 
 @pytest.mark.parametrize("options", [CR.CAUSAL, CR.CODEC, CR.CAUSAL | CR.DC_FILTER, CR.CODEC | CR.DC_FILTER])
-@pytest.mark.parametrize("delay", [0, 2, 4])
+@pytest.mark.parametrize("delay", [0, 1, 2, 3, 4])
 def test_the_six_scripts(options, delay):
     lost = CR.lost_matrix()
     fec_seen = False
@@ -162,7 +162,7 @@ def test_literal_traces(who):
 
 # -- invariants (tools/conceal_plan_check.cpp asserts the same in C++) ------------------------------
 
-@pytest.mark.parametrize("delay", [0, 2, 4])
+@pytest.mark.parametrize("delay", [0, 1, 2, 3, 4])
 def test_invariants(delay):
     buf = CR.plc_buf_size(delay)
     fills = {0} | set(range(80, buf + 1, 160))

@@ -34,13 +34,16 @@ def open_batch(B, run="causal"):
 
 class Driver:
     """Stream s of the batch plays script scripts[s], each stream at its own
-    position: the FEC events before a tick, then the tick."""
+    position: the FEC events before a tick, then the tick.  fx: another
+    table of the fixture's shape (lost, fec_events, pcm_in and `run`_pcm, a
+    row per script); rows(script, k): the k-th FEC frame a script adds."""
 
-    def __init__(self, b, scripts, device):
+    def __init__(self, b, scripts, device, fx=None, rows=None):
         self.b, self.scripts, self.device = b, list(scripts), device
         self.pos = np.zeros(b.B, int)
         self.nfec = np.zeros(b.B, int)
-        self.fx = CR.fixture()
+        self.fx = CR.fixture() if fx is None else fx
+        self.rows = (lambda sc, k: fec_row(k)) if rows is None else rows
         self.d_pcm = b.device_alloc(b.B * 320) if device else None
 
     def restart(self, s):
@@ -60,7 +63,7 @@ class Driver:
             elif ev == -1:
                 b.conceal_fec_add(s, None)
             for _ in range(max(0, ev)):
-                b.conceal_fec_add(s, fec_row(self.nfec[s]))
+                b.conceal_fec_add(s, self.rows(sc, self.nfec[s]))
                 self.nfec[s] += 1
             lost[s] = fx["lost"][sc, t]
             pcm[s] = fx["pcm_in"][sc, t]

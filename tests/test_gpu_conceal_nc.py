@@ -28,13 +28,14 @@ def open_batch(B, run):
 
 class Driver:
     """Stream s of the batch plays script scripts[s] of a run, each stream at
-    its own position: the FEC events before a tick, then the tick."""
+    its own position: the FEC events before a tick, then the tick.  fx:
+    another table of the fixture's shape, a row per script."""
 
-    def __init__(self, b, run, scripts, device):
+    def __init__(self, b, run, scripts, device, fx=None):
         self.b, self.run, self.scripts, self.device = b, run, list(scripts), device
         self.pos = np.zeros(b.B, int)
         self.nfec = np.zeros(b.B, int)
-        self.fx = NR.fixture()
+        self.fx = NR.fixture() if fx is None else fx
         self.d_pcm = b.device_alloc(b.B * 320) if device else None
 
     def restart(self, s):
